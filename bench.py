@@ -14,6 +14,23 @@ Inputs are resident in HBM before the timed region.  Prints ONE JSON line on ran
 `python bench.py --gpus N` without a torchrun environment re-launches itself under
 `python -m torch.distributed.run` with N ranks (one per GPU, RCCL).
 
+A plain run does what the headline figure needs and nothing else: set-up, the untimed pre-warm
+replay, the W warm-up and the K timed steps, `--dump-outputs`, the line (`metric`, `value`,
+`unit`, `ms_per_step` = milliseconds per timed step, `dtype`, launch path, config).  `--full` adds
+the figures that take runs of their own, all measured after the timed region: `roofline`
+(HIP events around the dominant kernel in eager steps), the torch.profiler kernel sum of one
+eager step, the extra legs (eager / reference train loop / fp32 ms_per_step), `cpu_baseline` and
+`parity`.
+
+`--dump-outputs DIR` writes what the timed path computed in its LAST timed step, as .npy files:
+a train config `loss.npy` (float64) plus `grads.npy` / `params.npy` (float32: the gradients the
+step left and the parameters after its SGD update, concatenated in `model.parameters()` order);
+an inference config `logits.npy` (float32).  An array larger than DUMP_SAMPLE elements is
+replaced by a fixed, seeded sample of them (the same positions in every run).  The pre-warm
+length follows the clock, so the model and optimizer state are restored to the post-capture
+snapshot after it and the device generator (Dropout masks) is re-seeded: with the same
+arguments the last timed step sees the same inputs in every run.
+
 Launch path: the step issues ~1400 kernels, and issued one by one from Python the host is the
 bottleneck (BENCH_r01: 39 ms/step against 33 ms of kernels).  With one GPU the whole step
 (forward, loss, backward, SGD) is therefore captured ONCE into a HIP graph (torch.cuda.CUDAGraph
@@ -57,6 +74,8 @@ sys.path.insert(0, ROOT)
 H, W, BATCH = 1025, 2049, 2
 FLOP_FWD_BWD_PER_IMAGE = 2.50935e12   # conv FLOPs, 3x fwd - first-layer dgrad
 MFMA_BF16_PEAK = 2.5e15               # MI355X dense bf16 (MI355X_MICROARCH.md)
+DUMP_SAMPLE = 1 << 21                 # --dump-outputs: elements per array at most (8 MB float32)
+DUMP_SEED = 0                         # --dump-outputs: the sample's positions
 
 C3 = ["DATASET.NAME", "cityscape", "TRAIN.BATCH_SIZE", str(BATCH), "TRAIN.CROP_SIZE", "769",
       "TEST.CROP_SIZE", "(1025, 2049)", "SOLVER.LR", "0.02", "MODEL.MODEL_NAME", "DeepLabV3_Plus",
@@ -411,6 +430,44 @@ def rocprof_fraction(args, flops_per_step, peak_tflops):
         return {"frac_rocprof_error": repr(e)[:200]}
 
 
+def train_state(model, opt):
+    """Every tensor a train step changes: parameters, buffers (BatchNorm running statistics and
+    counters) and the optimizer's momentum buffers.  `state_dict()` values alias the live tensors
+    (and share their version counters, so an in-place copy invalidates the weight-pack cache)."""
+    ts = list(model.state_dict().values())
+    for st in opt.state.values():
+        ts += [v for v in st.values() if torch.is_tensor(v)]
+    return ts
+
+
+def _sample(t):
+    """`t` flattened to float32 on the host: all of it, or DUMP_SAMPLE elements at fixed seeded
+    positions when it is larger."""
+    flat = t.detach().reshape(-1)
+    n = flat.numel()
+    if n > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(path, train, out, model):
+    """--dump-outputs: what the last timed step computed (see the module docstring)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if train:
+        params = [p for p in model.parameters() if p.grad is not None]
+        arrays = {"loss": np.asarray([out.detach().double().item()], dtype=np.float64),
+                  "grads": _sample(torch.cat([p.grad.reshape(-1).float() for p in params])),
+                  "params": _sample(torch.cat([p.detach().reshape(-1).float() for p in params]))}
+    else:
+        logits = out if isinstance(out, torch.Tensor) else out.float()  # (a pending LogitsView)
+        arrays = {"logits": _sample(logits)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -432,6 +489,11 @@ def main():
                          "path against the oracle step the cpu_baseline leg runs)")
     ap.add_argument("--prewarm-seconds", type=float, default=10.0,
                     help="continuous untimed replay before the warm-up + timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own, after the timed region: "
+                         "roofline, profiler kernel sum, extra legs, cpu_baseline, parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
     conf = CONFIGS[args.config]
     batch, train = conf["batch"], conf["train"]
@@ -601,7 +663,6 @@ def main():
                                  "all-reduce after backward\n" % (e,))
                 grad_overlap = None
 
-    timer = GemmTimer()
     # ---- launch path: one HIP graph of the whole step (single GPU), else eager
     graph, graph_err = None, None
     use_graph = (not multi or not train or dp_mode == "native") and not args.no_graph \
@@ -638,6 +699,12 @@ def main():
             return out if train else out[0]
         return step()
 
+    # the state the warm-up and timed steps start from, whatever the pre-warm's length
+    snapshot = None
+    if train:
+        live = train_state(model, opt)
+        snapshot = [t.clone() for t in live]
+
     # Device pre-conditioning (untimed, reported as "prewarm_steps"): a fresh box occasionally ran
     # its first 0.5 s of steps ~25 % slow (clock / power-state ramp, lazy kernel-module loads,
     # allocator growth) — a whole default-length bench fits into that window.  Run 20 extra
@@ -661,6 +728,13 @@ def main():
         run_step()
     torch.cuda.synchronize()
     prewarm += 5
+    if snapshot is not None:
+        with torch.no_grad():
+            for t, s in zip(live, snapshot):
+                t.copy_(s)
+        del snapshot, live
+        SF.note_running_stats_changed()
+    torch.cuda.manual_seed(0)  # Dropout masks (graph replays read the generator's offset too)
     for _ in range(args.warmup):
         run_step()
     if world > 1:
@@ -687,91 +761,67 @@ def main():
     loss_value = float(loss.item()) if train else float(loss.float().abs().mean().item())
     if hasattr(comm, "check"):
         comm.check()  # a peer that stopped publishing its statistics invalidates the run: raise
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train, loss, model)
     kernel_ms, n_kernels = (None, None)
-    # per-launch HIP events of the dominant kernel: three EAGER steps (same kernels, same shapes)
-    # AFTER the timed region — event pairs around every launch slow the launch-bound eager path
-    # itself down (2 x 157 timed events per step), so they must not sit in the timed steps of an
-    # eager (N > 1) run either
+    timer, extra = None, {}
     roofline_steps = 3
-    if graph is not None:
-        if train:
-            graph.release()
-        step()
-    torch.cuda.synchronize()
-    timer.active = True
-    for _ in range(roofline_steps):
-        # An eager step is launch-bound (the host needs longer to issue the ~1200 launches
-        # than the GPU to run them), and an event pair around a launch then also measures
-        # the queue running dry.  Give the host a head start: the GPU spins ~60 ms first, so
-        # every kernel of the step is already queued when its turn comes and e0 -> e1 is the
-        # kernel's duration alone.
-        torch.cuda.synchronize()
-        try:
-            torch.cuda._sleep(int(1.5e8))
-        except Exception:  # noqa: BLE001 — no spin kernel in this build: measure as is
-            pass
-        step()
-    torch.cuda.synchronize()
-    timer.active = False
-    if os.environ.get("SEG_BENCH_HOST_PROFILE") == "1":
-        # where the host time of an eager step goes (stderr; diagnostics for the N > 1 path).
-        # EVERY rank runs the extra steps (they issue collectives); rank 0 prints.
-        import cProfile
-        import pstats
-        pr = cProfile.Profile()
-        pr.enable()
-        for _ in range(3):
+    if args.full:
+        # per-launch HIP events of the dominant kernel: three EAGER steps (same kernels, same
+        # shapes) AFTER the timed region — event pairs around every launch slow the launch-bound
+        # eager path itself down (2 x 157 timed events per step), so they must not sit in the
+        # timed steps of an eager (N > 1) run either
+        timer = GemmTimer()
+        if graph is not None:
+            if train:
+                graph.release()
             step()
         torch.cuda.synchronize()
-        pr.disable()
-        if rank == 0:
-            pstats.Stats(pr, stream=sys.stderr).sort_stats("tottime").print_stats(25)
-    # one EAGER step under the profiler (roctracer does not see the nodes of a replayed graph):
-    # sum of its kernel durations / the timed ms_per_step -> gpu_busy_frac
-    if rank == 0 and world == 1:
-        kernel_ms, n_kernels = kernel_time_of_one_step(step)
-
-    extra = {}
-    if rank == 0 and world == 1 and train and not args.no_extra_legs:
-        extra = extra_legs(args, conf, model, opt, images, targets, step, loss_fn, dev, graph)
+        timer.active = True
+        for _ in range(roofline_steps):
+            # An eager step is launch-bound (the host needs longer to issue the ~1200 launches
+            # than the GPU to run them), and an event pair around a launch then also measures
+            # the queue running dry.  Give the host a head start: the GPU spins ~60 ms first, so
+            # every kernel of the step is already queued when its turn comes and e0 -> e1 is the
+            # kernel's duration alone.
+            torch.cuda.synchronize()
+            try:
+                torch.cuda._sleep(int(1.5e8))
+            except Exception:  # noqa: BLE001 — no spin kernel in this build: measure as is
+                pass
+            step()
+        torch.cuda.synchronize()
+        timer.active = False
+        if os.environ.get("SEG_BENCH_HOST_PROFILE") == "1":
+            # where the host time of an eager step goes (stderr; diagnostics for the N > 1
+            # path).  EVERY rank runs the extra steps (they issue collectives); rank 0 prints.
+            import cProfile
+            import pstats
+            pr = cProfile.Profile()
+            pr.enable()
+            for _ in range(3):
+                step()
+            torch.cuda.synchronize()
+            pr.disable()
+            if rank == 0:
+                pstats.Stats(pr, stream=sys.stderr).sort_stats("tottime").print_stats(25)
+        # one EAGER step under the profiler (roctracer does not see the nodes of a replayed
+        # graph): sum of its kernel durations / the timed ms_per_step -> gpu_busy_frac
+        if rank == 0 and world == 1:
+            kernel_ms, n_kernels = kernel_time_of_one_step(step)
+        if rank == 0 and world == 1 and train and not args.no_extra_legs:
+            extra = extra_legs(args, conf, model, opt, images, targets, step, loss_fn, dev, graph)
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         value = world * batch * args.steps / elapsed
-        flops, secs, launches = timer.result()
-        achieved = flops / secs / 1e12 if secs > 0 else 0.0
-        traffic = traffic_src = None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath) and args.config == "c3":
-            tj = json.load(open(tpath))
-            traffic = tj.get("conv_gemm_glds_bytes_per_launch")
-            traffic_src = tj.get("source")
-        fa, sa, la = timer.result_all()
-        # the roofline kernel: C3's dominant kernel is the direct-to-LDS 1x1 GEMM; the other
-        # configs are led by other members of the conv GEMM family (HRNet / MobileNetV2 barely run
-        # the 256-wide kernel at all — r04's c5 line said frac 0.0 of a kernel it never launched):
-        # there the figure is taken over ALL forward / data-gradient conv GEMM launches, and
-        # `top_kernels` names what the step actually spends its time in
-        roof_kernel = "conv_gemm_glds_kernel + conv_gemm_glds4_kernel (bf16, direct-to-LDS 1x1 GEMM)" if args.dtype == "bf16" \
-            else "conv_gemm_px256_kernel<fp32>"
-        if args.config != "c3" or launches == 0:
-            roof_kernel = "conv_gemm_* (all forward / data-gradient convolution GEMM launches)"
-            flops, secs, launches = fa, sa, la
-            achieved = flops / secs / 1e12 if secs > 0 else 0.0
         full = (args.height, args.width) == (conf["h"], conf["w"])
-        peak = MFMA_BF16_PEAK / 1e12 if args.dtype == "bf16" else 157.3
         line = {
             "metric": conf["metric"],
             "value": value, "unit": "images/sec", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "prewarm_steps": prewarm, "ms_per_step": ms,
             "higher_is_better": True, "scaling": "weak",
             "launch": "hip_graph" if graph is not None else "eager",
-            # (an EAGER step under torch.profiler: kernel count and the sum of their durations —
-            # not comparable with the replayed step's wall time, so no ratio is formed from it)
-            "eager_profile_kernel_ms_per_step": kernel_ms, "kernels_per_step": n_kernels,
-            # busy fraction of the REPLAYED step: kernel durations / wall span of one rocprofv3
-            # kernel trace of this command (tools/rocprof_roofline.py), when profiles/ holds one
-            "gpu_busy_frac": _graph_busy(),
             "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "config": {"workload": "%s @%dx%d, batch %d/GPU (%s)"
                                    % (conf["workload"], args.height, args.width, batch, conf["tag"]),
@@ -791,29 +841,60 @@ def main():
             "model_flop_fraction_of_bf16_mfma_peak":
                 value / world * FLOP_FWD_BWD_PER_IMAGE / MFMA_BF16_PEAK
                 if (full and args.config == "c3") else None,
-            "roofline": {"bound": "mfma", "kernel": roof_kernel,
-                         "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": achieved / peak,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "launches_per_step": launches / max(roofline_steps, 1),
-                         "kernel_ms_per_step": secs * 1e3 / max(roofline_steps, 1),
-                         "timing": "HIP events around each launch, %d eager steps with the launch queue kept "
-                                   "full (GPU spin-wait head start) after the timed %s"
-                                   % (roofline_steps, "graph replays" if graph is not None
-                                      else "eager steps"),
-                         "all_gemm_achieved": fa / sa / 1e12 if sa > 0 else 0.0,
-                         "all_gemm_launches_per_step": la / max(roofline_steps, 1),
-                         "all_gemm_ms_per_step": sa * 1e3 / max(roofline_steps, 1)},
         }
-        if TOP_KERNELS:
-            line["roofline"]["top_kernels"] = list(TOP_KERNELS)
-        line.update(extra)
-        rp = rocprof_fraction(args, flops / max(roofline_steps, 1), peak)
-        if rp:
-            line["roofline"].update(rp)
         if graph_err:
             line["hip_graph_error"] = graph_err
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            flops, secs, launches = timer.result()
+            achieved = flops / secs / 1e12 if secs > 0 else 0.0
+            traffic = traffic_src = None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tpath) and args.config == "c3":
+                tj = json.load(open(tpath))
+                traffic = tj.get("conv_gemm_glds_bytes_per_launch")
+                traffic_src = tj.get("source")
+            fa, sa, la = timer.result_all()
+            # the roofline kernel: C3's dominant kernel is the direct-to-LDS 1x1 GEMM; the other
+            # configs are led by other members of the conv GEMM family (HRNet / MobileNetV2 barely
+            # run the 256-wide kernel at all — r04's c5 line said frac 0.0 of a kernel it never
+            # launched): there the figure is taken over ALL forward / data-gradient conv GEMM
+            # launches, and `top_kernels` names what the step actually spends its time in
+            roof_kernel = "conv_gemm_glds_kernel + conv_gemm_glds4_kernel (bf16, direct-to-LDS 1x1 GEMM)" \
+                if args.dtype == "bf16" else "conv_gemm_px256_kernel<fp32>"
+            if args.config != "c3" or launches == 0:
+                roof_kernel = "conv_gemm_* (all forward / data-gradient convolution GEMM launches)"
+                flops, secs, launches = fa, sa, la
+                achieved = flops / secs / 1e12 if secs > 0 else 0.0
+            peak = MFMA_BF16_PEAK / 1e12 if args.dtype == "bf16" else 157.3
+            line.update({
+                # (an EAGER step under torch.profiler: kernel count and the sum of their durations
+                # — not comparable with the replayed step's wall time, so no ratio is formed)
+                "eager_profile_kernel_ms_per_step": kernel_ms, "kernels_per_step": n_kernels,
+                # busy fraction of the REPLAYED step: kernel durations / wall span of one
+                # rocprofv3 kernel trace of this command (tools/rocprof_roofline.py), when
+                # profiles/ holds one
+                "gpu_busy_frac": _graph_busy(),
+                "roofline": {"bound": "mfma", "kernel": roof_kernel,
+                             "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                             "frac": achieved / peak,
+                             "traffic": traffic, "traffic_source": traffic_src,
+                             "launches_per_step": launches / max(roofline_steps, 1),
+                             "kernel_ms_per_step": secs * 1e3 / max(roofline_steps, 1),
+                             "timing": "HIP events around each launch, %d eager steps with the launch "
+                                       "queue kept full (GPU spin-wait head start) after the timed %s"
+                                       % (roofline_steps, "graph replays" if graph is not None
+                                          else "eager steps"),
+                             "all_gemm_achieved": fa / sa / 1e12 if sa > 0 else 0.0,
+                             "all_gemm_launches_per_step": la / max(roofline_steps, 1),
+                             "all_gemm_ms_per_step": sa * 1e3 / max(roofline_steps, 1)},
+            })
+            if TOP_KERNELS:
+                line["roofline"]["top_kernels"] = list(TOP_KERNELS)
+            line.update(extra)
+            rp = rocprof_fraction(args, flops / max(roofline_steps, 1), peak)
+            if rp:
+                line["roofline"].update(rp)
+        if args.full and not args.no_cpu_baseline and world == 1:
             ch, cw = (int(v) for v in args.cpu_baseline_size.lower().split("x"))
             keep = {} if (args.config in ("c3", "c4") and train and (ch, cw) == (args.height, args.width)
                           and not args.no_parity) else None

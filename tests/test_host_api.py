@@ -54,10 +54,9 @@ def test_cfg_semantics():
     assert cfg.SEED == 1024 and not cfg.is_immutable()
 
 
-def test_cfg_reads_reference_yaml_if_present():
-    path = "/root/reference/configs/cityscapes_deeplabv3_plus.yaml"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present")
+def test_cfg_reads_reference_yaml_if_present(golden_dir):
+    """The reference's C3 yaml, as stored under tests/golden/ (same values, same spelling)."""
+    path = os.path.join(golden_dir, "cityscapes_deeplabv3_plus.yaml")
     from segmentron_amd.config import cfg, reset_cfg
     reset_cfg()
     cfg.update_from_file(path)

@@ -18,7 +18,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   echo "pytest rc=$prc"; grep -E "^(FAILED|ERROR)|passed|failed|Fatal" $OUT/pytest.log | tail -40
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-  timeout 900 python bench.py ${BENCH_ARGS:---steps 20 --warmup 5} > $OUT/bench.json 2> $OUT/bench.err
+  timeout 900 python bench.py ${BENCH_ARGS:---steps 20 --warmup 5 --full} > $OUT/bench.json 2> $OUT/bench.err
   echo "bench rc=$?"; cat $OUT/bench.json; tail -5 $OUT/bench.err
 fi
 if [ "${SKIP_PROF:-0}" != "1" ]; then
