@@ -680,6 +680,9 @@ int launch_dw_slide_fwd(int dtype, const void* x, long ldx, int N, int H, int W,
   a.N = N; a.H = H; a.W = W; a.C = C; a.pro_mode = pro_mode;
   slide_geom(a, N, H, W, C);
   SEG_REQUIRE(slide_mode_ok(pro_mode), "dwconv (slide): unsupported prologue mode %d", pro_mode);
+  // (every access is a 4-channel vector: 16 bytes fp32 / 8 bytes bf16 at pixel * ld + c)
+  SEG_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0,
+              "dwconv (slide): C/ldx/ldy must be multiples of 4");
   SEG_REQUIRE(stat_partial == nullptr || rows == N * a.nstrips * a.nwblk,
               "dwconv (slide): %d partial rows, the launch writes %d (seg_dwconv_grid_y)", rows,
               N * a.nstrips * a.nwblk);
@@ -700,6 +703,9 @@ int launch_dw_slide_bwd(int dtype, const void* dy, long lddy, const void* x, lon
   a.N = N; a.H = H; a.W = W; a.C = C; a.pro_mode = pro_mode;
   slide_geom(a, N, H, W, C);
   SEG_REQUIRE(slide_mode_ok(pro_mode), "dwconv bwd (slide): unsupported prologue mode %d", pro_mode);
+  SEG_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && lddy % 4 == 0 && ldg % 4 == 0 &&
+                  (res == nullptr || ldr % 4 == 0),
+              "dwconv bwd (slide): C/ldx/lddy/ldg/ldr must be multiples of 4");
   SEG_REQUIRE(rows == N * a.nstrips * a.nwblk,
               "dwconv bwd (slide): %d partial rows, the launch writes %d (seg_dwconv_grid_y)", rows,
               N * a.nstrips * a.nwblk);
