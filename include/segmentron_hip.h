@@ -339,7 +339,7 @@ int seg_nchw_to_nhwc_pad(int dtype, const float* x, int N, int Cin, int H, int W
  * vector-padded pitch); target: int64 [N, H, W]; loss_out: float32[2] = (mean loss, 1 / number
  * of valid pixels); ws: >= 2 * seg_upsample_ce_blocks(N, H, W) doubles.  Backward: dlo
  * [N, Hi, Wi, lddlo] in `dtype` (channels >= C written as zeros) = grad_out[0] * dLoss/dlo,
- * up-sampling factors up to 8.1 (output-stride-4 and -8 heads).  Deterministic (fixed-order float64 / gather reductions). */
+ * up-sampling factors up to 16.1 (output-stride-4, -8 and -16 heads).  Deterministic (fixed-order float64 / gather reductions). */
 int seg_upsample_ce_blocks(int N, int H, int W);
 int seg_upsample_ce_fwd(int dtype, const void* lo, long ld, int N, int Hi, int Wi, int C,
                         const long* target, int H, int W, long ignore_index, int align_corners,
@@ -348,6 +348,53 @@ int seg_upsample_ce_bwd(int dtype, const void* lo, long ld, int N, int Hi, int W
                         const long* target, int H, int W, long ignore_index, int align_corners,
                         const float* loss_out, const float* grad_out, void* dlo, long lddlo,
                         void* stream);
+
+/* ---- PointRend point head (segmentron/models/pointrend.py:32-195, csrc/pointrend.hip) ---------
+ * Maps are addressed through strides: element (n, pixel h*W + w, channel c) at
+ * x + n*sn + (h*W + w)*sp + c*sc (NHWC activation: sn = H*W*ld, sp = ld, sc = 1; NCHW float32:
+ * sn = C*H*W, sp = 1, sc = H*W).  pts: fp32 [N][P][2] (width, height) in [0, 1].  Point rows:
+ * [N*P][ld] in their own dtype.  Deterministic: no float atomics.
+ *   seg_point_sample      rows y[n*P + p][col + c] = F.grid_sample(x, 2p - 1, align_corners=False,
+ *                         padding 'zeros'), bilinear or (nearest = 1) std::nearbyint taps; the
+ *                         coarse and fine features of pointrend.py:63-66 land side by side
+ *   seg_point_sample_bwd  dx NHWC [N,H,W,lddx] channels [0, C) (every pixel written) = the
+ *                         bilinear backward of rows g[.][col + c]; ws: seg_point_sample_bwd_ws ints
+ *                         (points bucketed by cell, each pixel sums its points in a fixed order)
+ *   seg_point_uncertainty u = -(top1 - top2) of the C channels: per pixel (pts = NULL, u [N][H*W])
+ *                         or of the rank-0 / rank-1 planes interpolated at the points (u [N][P])
+ *   seg_point_topk        idx int64 [N][K] = the K largest of keys [N][L], ties to the lower
+ *                         index, ascending; ws: seg_point_topk_ws ints (radix select)
+ *   seg_point_coords      over != NULL: pts[n] = (over[n][idx[n][j]] for j < K, then cover[n]);
+ *                         over == NULL: pixel centres of idx on an H x W grid (pointrend.py:170-172)
+ *   seg_point_scatter     y[n, idx[n][p], c] = rend[n*P + p][c] (float32 map, strides as above)
+ *   seg_point_resize      F.interpolate(x, (Ho, Wo), 'bilinear', align_corners) -> float32 NCHW
+ *   seg_point_ce_fwd/bwd  mean NLL of log_softmax over the C columns of rows x against target
+ *                         int64 [R] (ignore_index; targets outside [0, C) are ignored too);
+ *                         loss_out float32[2] = (loss, 1 / valid rows), NaN when none is valid;
+ *                         ws >= 2 * seg_point_ce_blocks(R) doubles */
+int seg_point_sample(int dtype_x, const void* x, long sn, long sp, long sc, int N, int H, int W,
+                     int C, const float* pts, int P, int nearest, int dtype_y, void* y, long ldy,
+                     int col, void* stream);
+int seg_point_sample_bwd_ws(int N, int H, int W, int P);
+int seg_point_sample_bwd(int dtype_g, const void* g, long ldg, int col, const float* pts, int N,
+                         int P, int H, int W, int C, int dtype_x, void* dx, long lddx, int* ws,
+                         void* stream);
+int seg_point_uncertainty(int dtype, const void* x, long sn, long sp, long sc, int N, int H, int W,
+                          int C, const float* pts, int P, float* u, void* stream);
+int seg_point_topk_ws(int N, long L);
+int seg_point_topk(const float* keys, int N, long L, int K, long* idx, int* ws, void* stream);
+int seg_point_coords(const float* over, const long* idx, int N, int L, int K, const float* cover,
+                     int P, int H, int W, float* pts, void* stream);
+int seg_point_scatter(int dtype_r, const void* rend, long ldr, const long* idx, int N, int P,
+                      int C, float* y, long sn, long sp, long sc, void* stream);
+int seg_point_resize(int dtype, const void* x, long sn, long sp, long sc, int N, int Hi, int Wi,
+                     int C, float* y, int Ho, int Wo, int align_corners, void* stream);
+int seg_point_ce_blocks(long R);
+int seg_point_ce_fwd(int dtype, const void* x, long ldx, long R, int C, const long* target,
+                     long ignore_index, double* ws, float* loss_out, void* stream);
+int seg_point_ce_bwd(int dtype, const void* x, long ldx, long R, int C, const long* target,
+                     long ignore_index, const float* loss_out, const float* grad_out, void* dx,
+                     long lddx, void* stream);
 
 /* ---- stride-2 depthwise 3x3 (padding 1, dilation 1): fused backward --------------------------
  * One pass over dy [N,(H+1)/2,(W+1)/2,C] and x [N,H,W,C] (+ prologue): g = masked data gradient,

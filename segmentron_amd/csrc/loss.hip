@@ -324,6 +324,14 @@ static_assert(ce_bwd_lds<32, CE8_LT32, CE8_HT32, CE_CH32>() <= 53 * 1024, "LDS b
 constexpr float CE_MAX_SCALE = 4.1f, CE8_MAX_SCALE = 8.1f;
 static_assert((CE_LT24 + 1.5f) * CE_MAX_SCALE + 5 <= CE_HT24 + 1 && (CE_LT32 + 1.5f) * CE_MAX_SCALE + 5 <= CE_HT32 + 1, "");
 static_assert((CE8_LT24 + 1.5f) * CE8_MAX_SCALE + 5 <= CE8_HT24 && (CE8_LT32 + 1.5f) * CE8_MAX_SCALE + 5 <= CE8_HT32, "");
+// up to 16.1x (output-stride-16 logits resized to the crop: PointRend's coarse-logit loss,
+// segmentron/solver/loss.py:374): 2 x 2 low-resolution tiles, (2 + 1.5) * 16.1 + 5 = 61.4 rows; the
+// chunk shrinks to 8 (6) rows so that three blocks still share a CU
+constexpr int CE16_LT = 2, CE16_HT = 62, CE16_CH24 = 8, CE16_CH32 = 6;
+constexpr float CE16_MAX_SCALE = 16.1f;
+static_assert(ce_bwd_lds<24, CE16_LT, CE16_HT, CE16_CH24>() <= 53 * 1024, "LDS budget (3 blocks/CU)");
+static_assert(ce_bwd_lds<32, CE16_LT, CE16_HT, CE16_CH32>() <= 53 * 1024, "LDS budget (3 blocks/CU)");
+static_assert((CE16_LT + 1.5f) * CE16_MAX_SCALE + 5 <= CE16_HT, "");
 
 template <typename T, int NC, int LT, int HT, int CH>
 static int launch_ce_bwd(int blocks, hipStream_t st, const CeArgs& a, const float* loss_out,
@@ -387,17 +395,29 @@ extern "C" int seg_upsample_ce_bwd(int dtype, const void* lo, long ld, int N, in
   SEG_REQUIRE(C >= 1 && C <= 32 && ld % vec == 0 && lddlo >= C && lddlo <= 32,
               "upsample_ce_bwd: bad C / pitch (1 <= C <= lddlo <= 32)");
   SEG_REQUIRE(H >= Hi && W >= Wi, "upsample_ce_bwd: the fused loss is for UP-sampling heads");
-  // a low-res tile row is touched by at most HT_MAX output rows / columns up to 4.1x (8.1x)
+  // a low-res tile row is touched by at most HT_MAX output rows / columns up to 4.1x (8.1x, 16.1x)
   const float sh = host_scale(Hi, H, align_corners), sw = host_scale(Wi, W, align_corners);
   const float smin = fminf(sh > 0.f ? sh : 1.f, sw > 0.f ? sw : 1.f);
-  SEG_REQUIRE(1.f / smin <= CE8_MAX_SCALE,
+  SEG_REQUIRE(1.f / smin <= CE16_MAX_SCALE,
               "upsample_ce_bwd: scale factor %.2f too large for the fused backward", 1.f / smin);
-  const bool wide = 1.f / smin > CE_MAX_SCALE;  // 4.1x .. 8.1x: the small-tile instances
   CeArgs a;
   a.lo = lo; a.target = target; a.ld = ld; a.N = N; a.Hi = Hi; a.Wi = Wi; a.H = H; a.W = W;
   a.C = C; a.ignore = ignore_index; a.align = align_corners; a.sh = sh; a.sw = sw;
   hipStream_t st = (hipStream_t)stream;
   const int nc = C <= 24 ? 24 : 32;
+  if (1.f / smin > CE8_MAX_SCALE) {  // 8.1x .. 16.1x: the 2 x 2 tile instances
+    const int blocks16 = N * ((Hi + CE16_LT - 1) / CE16_LT) * ((Wi + CE16_LT - 1) / CE16_LT);
+    int rc16;
+    if (dtype == DT_BF16)
+      rc16 = nc == 24 ? launch_ce_bwd<bf16_t, 24, CE16_LT, CE16_HT, CE16_CH24>(blocks16, st, a, loss_out, grad_out, dlo, lddlo)
+                      : launch_ce_bwd<bf16_t, 32, CE16_LT, CE16_HT, CE16_CH32>(blocks16, st, a, loss_out, grad_out, dlo, lddlo);
+    else
+      rc16 = nc == 24 ? launch_ce_bwd<float, 24, CE16_LT, CE16_HT, CE16_CH24>(blocks16, st, a, loss_out, grad_out, dlo, lddlo)
+                      : launch_ce_bwd<float, 32, CE16_LT, CE16_HT, CE16_CH32>(blocks16, st, a, loss_out, grad_out, dlo, lddlo);
+    if (rc16) return rc16;
+    return check_launch("upsample_ce_bwd");
+  }
+  const bool wide = 1.f / smin > CE_MAX_SCALE;  // 4.1x .. 8.1x: the small-tile instances
   const int lt = wide ? (nc == 24 ? CE8_LT24 : CE8_LT32) : (nc == 24 ? CE_LT24 : CE_LT32);
   const int blocks = N * ((Hi + lt - 1) / lt) * ((Wi + lt - 1) / lt);
   int rc;

@@ -975,3 +975,172 @@ def cca_map(wt, b, transposed=False, gamma=None, res=None, want_raw=False):
     LIB.call("seg_cca_map", _DT[b.dtype], _p(wt), _p(b), ldb, N, H, W, C, int(bool(transposed)),
              _p(gamma), _p(res), ldres, _p(out), C, _p(raw), C, _stream())
     return (out, raw) if want_raw else out
+
+
+# ----------------------------------------------------------------------------- PointRend
+# A "map" is (tensor, sn, sp, sc, N, H, W, C): element (n, pixel, c) at n*sn + pixel*sp + c*sc.
+def map_nhwc(t):
+    """NHWC view (channel slice of a pitched buffer allowed) as a point-head map."""
+    N, H, W, C, ld = nhwc(t)
+    return (t, H * W * ld, ld, 1, N, H, W, C)
+
+
+def map_nchw(t):
+    """NCHW tensor (made contiguous) as a point-head map."""
+    if not t.is_cuda:
+        raise RuntimeError("segmentron_amd ops need HIP device tensors (no CPU fallback)")
+    if t.dim() != 4 or t.dtype not in _DT:
+        raise RuntimeError("expected a float32 / bfloat16 NCHW tensor, got %s %s"
+                           % (tuple(t.shape), t.dtype))
+    t = t.contiguous()
+    N, C, H, W = t.shape
+    return (t, C * H * W, 1, H * W, N, H, W, C)
+
+
+def _points(pts, N):
+    if not pts.is_cuda or pts.dtype != torch.float32 or pts.dim() != 3 or pts.shape[0] != N \
+            or pts.shape[2] != 2:
+        raise RuntimeError("points must be a float32 HIP tensor [%d, P, 2], got %s %s"
+                           % (N, tuple(pts.shape), pts.dtype))
+    return pts.contiguous()
+
+
+def _rows(t):
+    """-> (R, C, ld) of a 2-d row view [R, C] with row pitch ld."""
+    if not t.is_cuda or t.dim() != 2 or (t.stride(1) != 1 and t.shape[1] > 1):
+        raise RuntimeError("expected a 2-d HIP row view, got %s strides %s"
+                           % (tuple(t.shape), t.stride()))
+    return t.shape[0], t.shape[1], t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def point_sample(m, pts, out=None, col=0, nearest=False):
+    """grid_sample of map m at pts [N, P, 2] into rows out[N*P, ld][:, col:col+C] (allocated
+    float32 [N*P, C] when None)."""
+    t, sn, sp, sc, N, H, W, C = m
+    pts = _points(pts, N)
+    P = pts.shape[1]
+    if out is None:
+        out = torch.empty((N * P, C), dtype=torch.float32, device=t.device)
+    R, _, ld = _rows(out)
+    assert R == N * P and out.shape[1] >= col + C
+    LIB.call("seg_point_sample", _DT[t.dtype], _p(t), sn, sp, sc, N, H, W, C, _p(pts), P,
+             int(bool(nearest)), _DT[out.dtype], _p(out), ld, col, _stream())
+    return out
+
+
+def point_sample_bwd(g, col, C, pts, in_hw, dtype, pitch=None):
+    """Bilinear backward of point_sample: rows g[N*P, ld][:, col:col+C] -> NHWC dx
+    [N, H, W, pitch][..., :C] in `dtype` (every pixel written)."""
+    N, P = pts.shape[0], pts.shape[1]
+    pts = _points(pts, N)
+    H, W = in_hw
+    R, _, ldg = _rows(g)
+    assert R == N * P and g.shape[1] >= col + C
+    nws = LIB.query("seg_point_sample_bwd_ws", N, H, W, P)
+    if nws < 0:
+        raise RuntimeError("point_sample_bwd: geometry too large")
+    ws = torch.empty(nws, dtype=torch.int32, device=g.device)
+    pitch = pitch or C
+    # the kernel writes channels [0, C): the pad of a pitched result is zeroed
+    dx = (torch.zeros if pitch > C else torch.empty)((N, H, W, pitch), dtype=dtype,
+                                                     device=g.device)
+    LIB.call("seg_point_sample_bwd", _DT[g.dtype], _p(g), ldg, col, _p(pts), N, P, H, W, C,
+             _DT[dtype], _p(dx), pitch, _p(ws), _stream())
+    return dx if pitch == C else dx[..., :C]
+
+
+def point_uncertainty(m, pts=None):
+    """-(top1 - top2) over the channels: per pixel ([N, H*W]) or at pts ([N, P], rank planes
+    interpolated)."""
+    t, sn, sp, sc, N, H, W, C = m
+    if pts is None:
+        P, u = 0, torch.empty((N, H * W), dtype=torch.float32, device=t.device)
+    else:
+        pts = _points(pts, N)
+        P = pts.shape[1]
+        u = torch.empty((N, P), dtype=torch.float32, device=t.device)
+    LIB.call("seg_point_uncertainty", _DT[t.dtype], _p(t), sn, sp, sc, N, H, W, C, _p(pts), P,
+             _p(u), _stream())
+    return u
+
+
+def point_topk(keys, K):
+    """int64 [N, K]: indices of the K largest of float32 keys [N, L] (ties: lower index), in
+    ascending order."""
+    if not keys.is_cuda or keys.dtype != torch.float32 or keys.dim() != 2:
+        raise RuntimeError("point_topk: keys must be a float32 HIP tensor [N, L]")
+    keys = keys.contiguous()
+    N, L = keys.shape
+    ws = torch.empty(LIB.query("seg_point_topk_ws", N, L), dtype=torch.int32, device=keys.device)
+    idx = torch.empty((N, K), dtype=torch.int64, device=keys.device)
+    LIB.call("seg_point_topk", _p(keys), N, L, K, _p(idx), _p(ws), _stream())
+    return idx
+
+
+def point_coords_train(over, idx, cover):
+    """[N, P, 2]: over[n, idx[n]] (importance points), then cover[n] (idx None: cover alone)."""
+    if idx is None:
+        return cover.contiguous()
+    N, L, _ = over.shape
+    over, cover = _points(over, N), _points(cover, N)
+    K = idx.shape[1]
+    P = K + cover.shape[1]
+    pts = torch.empty((N, P, 2), dtype=torch.float32, device=over.device)
+    LIB.call("seg_point_coords", _p(over), _p(idx.contiguous()), N, L, K, _p(cover), P, 0, 0,
+             _p(pts), _stream())
+    return pts
+
+
+def point_coords_grid(idx, hw):
+    """[N, K, 2]: centres of the pixels idx [N, K] of an H x W grid (pointrend.py:170-172)."""
+    N, K = idx.shape
+    H, W = hw
+    pts = torch.empty((N, K, 2), dtype=torch.float32, device=idx.device)
+    LIB.call("seg_point_coords", None, _p(idx.contiguous()), N, 0, K, None, K, H, W, _p(pts),
+             _stream())
+    return pts
+
+
+def point_scatter(rows, idx, m):
+    """m[n, idx[n, p], c] = rows[n*P + p, c] (m: float32 map, written in place)."""
+    t, sn, sp, sc, N, H, W, C = m
+    assert t.dtype == torch.float32
+    R, Cr, ldr = _rows(rows)
+    P = idx.shape[1]
+    assert R == N * P and Cr == C
+    LIB.call("seg_point_scatter", _DT[rows.dtype], _p(rows), ldr, _p(idx.contiguous()), N, P, C,
+             _p(t), sn, sp, sc, _stream())
+
+
+def point_resize(m, out_hw, align_corners=False):
+    """F.interpolate(map, out_hw, 'bilinear', align_corners) -> float32 NCHW [N, C, Ho, Wo]."""
+    t, sn, sp, sc, N, H, W, C = m
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    y = torch.empty((N, C, Ho, Wo), dtype=torch.float32, device=t.device)
+    LIB.call("seg_point_resize", _DT[t.dtype], _p(t), sn, sp, sc, N, H, W, C, _p(y), Ho, Wo,
+             int(bool(align_corners)), _stream())
+    return y
+
+
+def point_ce_fwd(rows, target, ignore_index):
+    """Mean cross-entropy of the rows [R, C] against int64 target [R] -> float32[2] = (loss,
+    1 / valid rows)."""
+    R, C, ld = _rows(rows)
+    if not target.is_cuda or target.dtype != torch.int64 or target.numel() != R:
+        raise RuntimeError("point_ce: target must be an int64 HIP tensor of %d elements" % R)
+    ws = torch.empty(2 * LIB.query("seg_point_ce_blocks", R), dtype=torch.float64,
+                     device=rows.device)
+    out = torch.empty(2, dtype=torch.float32, device=rows.device)
+    LIB.call("seg_point_ce_fwd", _DT[rows.dtype], _p(rows), ld, R, C, _p(target.contiguous()),
+             int(ignore_index), _p(ws), _p(out), _stream())
+    return out
+
+
+def point_ce_bwd(rows, target, ignore_index, loss_out, grad_out):
+    """-> d(loss)/d(rows) * grad_out, [R, C] in rows.dtype."""
+    R, C, ld = _rows(rows)
+    grad_out = grad_out.reshape(1).to(torch.float32).contiguous()
+    dx = torch.empty((R, C), dtype=rows.dtype, device=rows.device)
+    LIB.call("seg_point_ce_bwd", _DT[rows.dtype], _p(rows), ld, R, C, _p(target.contiguous()),
+             int(ignore_index), _p(loss_out), _p(grad_out), _p(dx), C, _stream())
+    return dx

@@ -7,3 +7,4 @@ from .hrnet_seg import HighResolutionNet  # noqa: F401
 from .ccnet import CCNet  # noqa: F401
 from .fast_scnn import FastSCNN  # noqa: F401
 from .danet import DANet  # noqa: F401
+from .pointrend import PointRend  # noqa: F401

@@ -19,8 +19,16 @@ def get_segmentation_model():
     if graph.transparent_graph_requested():
         # SEGMENTRON_HIP_GRAPH=1: train-mode forward / backward replay captured HIP graphs behind
         # the unchanged tools/train.py loop (segmentron_amd/graph.py TransparentTrainGraph)
-        graph.TransparentTrainGraph.install(model)
+        if getattr(model, "graph_capturable", True):
+            graph.TransparentTrainGraph.install(model)
+        elif type(model).__name__ not in _EAGER_NOTED:  # PointRend: data-dependent points
+            _EAGER_NOTED.add(type(model).__name__)
+            logging.info("SEGMENTRON_HIP_GRAPH=1: %s is not graph-captured, it runs eagerly"
+                         % type(model).__name__)
     return model
+
+
+_EAGER_NOTED = set()
 
 
 def load_model_pretrain(model):
