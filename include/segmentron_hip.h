@@ -194,6 +194,11 @@ int seg_bn_apply(int dtype, const void* x, long ldx, int mode_x, const float* sx
  * finalize: dgamma, dbeta and the coefficients c0,c1 of  dx = scale*g' - c0 - c1*x
  * apply   : dx (may alias g).  With mode lacking the affine bit: dx = g' (ReLU backward). */
 int seg_bn_bwd_grid_y(int dtype, int C, long M);
+/* Launch geometry of the row-tile kernels (seg_bn_apply, seg_bn_bwd_reduce, seg_bn_bwd_apply,
+ * seg_sum_n), pure host.  what: 0 = lanes (16-byte channel vectors) per row of a block, 1 = rows
+ * per block, 2 = threads per block, 3 = gridDim.x, 4 = gridDim.y of the apply kernels and
+ * seg_sum_n for M rows (the reduce has seg_bn_bwd_grid_y rows).  -1 on a bad argument. */
+int seg_ew_geom_query(int dtype, int C, long M, int what);
 int seg_bn_bwd_reduce(int dtype, const void* g, long ldg, const void* x, long ldx, int mode,
                       const float* scale, const float* shift, const float* chan_mul,
                       long rows_per_n, const void* elem_mul, long ldm, long M, int C,

@@ -1024,6 +1024,26 @@ extern "C" int seg_bn_bwd_grid_y(int dtype, int C, long M) {
   return (int)gy;
 }
 
+// Launch geometry of the row-tile kernels (seg_bn_apply, seg_bn_bwd_reduce, seg_bn_bwd_apply,
+// seg_sum_n) for C channels of `dtype` over M rows, pure host: what = 0 lanes (channel vectors)
+// per row of a block, 1 rows per block, 2 threads per block, 3 gridDim.x, 4 gridDim.y of the
+// apply kernels and seg_sum_n (the reduce: seg_bn_bwd_grid_y).  -1: bad dtype / C / M / what.
+extern "C" int seg_ew_geom_query(int dtype, int C, long M, int what) {
+  using namespace seg;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -1;
+  const int vec = dtype == DT_BF16 ? 8 : 4;
+  if (C < vec || C % vec != 0 || M < 1 || M >= (1L << 31)) return -1;
+  const EwGeom geo = ew_geom(C / vec);
+  switch (what) {
+    case 0: return geo.lpr;
+    case 1: return geo.rpb;
+    case 2: return geo.threads;
+    case 3: return geo.gx;
+    case 4: return (int)ew_grid2(geo, M).y;
+  }
+  return -1;
+}
+
 // partial[grid_y][2][C] = per-block (sum g', sum g'*x),  g' = g * chan_mul * relu_mask(mode)
 extern "C" int seg_bn_bwd_reduce(int dtype, const void* g, long ldg, const void* x, long ldx,
                                  int mode, const float* scale, const float* shift,

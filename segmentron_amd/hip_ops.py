@@ -482,6 +482,18 @@ def bn_bwd_reduce_partial(g, x, pro, chan_mul=None, elem_mul=None):
     return partial
 
 
+def ew_geom(dtype, C, M):
+    """Launch geometry of the row-tile kernels (bn_apply, bn_bwd_reduce_partial, bn_bwd_apply,
+    sum_n) for C channels of `dtype` over M rows (host only) -> dict: lanes per row and rows of a
+    block, threads, gx, gy (gridDim.y of the apply kernels / sum_n), gy_reduce (partial rows)."""
+    vals = [LIB.query("seg_ew_geom_query", _DT[dtype], C, M, k) for k in range(5)]
+    if min(vals) < 1:
+        raise ValueError("ew_geom: bad dtype / C / M: %s %d %d" % (dtype, C, M))
+    geo = dict(zip(("lanes", "rows", "threads", "gx", "gy"), vals))
+    geo["gy_reduce"] = LIB.query("seg_bn_bwd_grid_y", _DT[dtype], C, M)
+    return geo
+
+
 def bn_bwd_small(g, x, pro, count, mean, invstd, gamma, chan_mul=None, elem_mul=None,
                  training=True, out=None):
     """BatchNorm backward of a small tensor (<= SMALL_BN_ROWS samples per channel) in one

@@ -302,6 +302,15 @@ def test_kernel_selection_queries_of_the_c_library():
     assert q("seg_dwconv3x3_s2_grid_y", 128, 2, 513, 1025) == 768 // 4
     assert q("seg_dwconv_grid_y", BF16, 2048, 2, 65, 129, 1, 18, 0) == min(2 * 18 * 1, 768 // 64)
     assert q("seg_dwconv_grid_y", BF16, 2048, 2, 65, 129, 1, 6, 1) == min(2 * 6 * 1, 768 // 64)
+    # row-tile element-wise kernels (bn_apply / bn_bwd_reduce / bn_bwd_apply / sum_n): lanes per
+    # row, rows per block, threads, gridDim.x, gridDim.y — column blocks up to 32 channel vectors,
+    # whole rows up to 512 (728 channels: 182 x 2 / 91 x 4 lanes, 20 idle), column blocks above
+    geo = lambda dt, C, M: [q("seg_ew_geom_query", dt, C, M, k) for k in range(5)]
+    assert geo(F32, 72, 198) == [8, 32, 256, 3, 2] and geo(BF16, 256, 198) == [32, 8, 256, 1, 7]
+    assert geo(F32, 728, 16770) == [182, 2, 384, 1, 512] and geo(BF16, 728, 16770) == [91, 4, 384, 1, 512]
+    assert geo(F32, 2048, 100) == [512, 1, 512, 1, 25] and geo(F32, 2052, 100000) == [8, 32, 256, 65, 7]
+    assert q("seg_ew_geom_query", F32, 6, 10, 0) == -1 and q("seg_ew_geom_query", F32, 8, 10, 5) == -1
+    assert q("seg_bn_bwd_grid_y", F32, 728, 16770) == 256 and q("seg_bn_bwd_grid_y", F32, 2052, 100000) == 31
 
 
 def test_frozen_batchnorm_module_contract():

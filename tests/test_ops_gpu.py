@@ -559,27 +559,72 @@ def test_bn_apply_residual_and_channel_mask(dtype):
                  "bn_apply post_relu")
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
-@pytest.mark.parametrize("relu", [False, True])
-def test_bn_backward_matches_autograd(dtype, relu):
-    """relu(BN_train(x)) * mask consumed with gradient g: dx, dgamma, dbeta vs torch autograd"""
-    N, C, H, W = 2, 104, 9, 11
-    x = quant(rnd((N, C, H, W), 1) * 1.5 + 0.3, dtype)
-    gamma, beta = (torch.rand(C) + 0.5).requires_grad_(), rnd((C,), 3, 0.2).requires_grad_()
+BN_BWD_SHAPE = (2, 104, 9, 11)
+# 728 channels (whole-row blocks of the row-tile kernels: 182 x 2 lanes in fp32, 91 x 4 in bf16, 20
+# idle lanes): at 198 rows functional.bn_input_backward still takes the one-launch float64 route
+# (seg_bn_bwd_small: at most 1024 rows); 2 x 23 x 23 = 1058 rows is the smallest map that goes
+# reduce -> finalize -> apply.  The test asserts which route ran.
+BN_BWD_SMALL_728, BN_BWD_ROW = (2, 728, 9, 11), (2, 728, 23, 23)
+# Seed of x.  For the 728-channel shapes gamma comes from a fixed generator (not, as for the first
+# shape, from the global one that conftest.py seeds from the test's name), so the data the guard
+# below sees depends on (shape, dtype) alone and _bn_backward_reference can be called outside
+# pytest.  With up to 770 000 values the smallest |BN(x)| of the reference is usually below 1e-5
+# (seed 1: 3e-7 .. 5e-6, a ReLU mask that fp32 rounding can flip); these seeds keep it above
+# (2.3e-5, 2.4e-5, 1.3e-5, 1.7e-5), which the reference half asserts.
+BN_BWD_SEED = {(BN_BWD_SMALL_728, torch.float32): 1, (BN_BWD_SMALL_728, torch.bfloat16): 5,
+               (BN_BWD_ROW, torch.float32): 368, (BN_BWD_ROW, torch.bfloat16): 4151}
+
+
+def _bn_backward_reference(dtype, relu, shape=BN_BWD_SHAPE):
+    """CPU half of test_bn_backward_matches_autograd (no device needed): the data, torch
+    autograd's float64 gradients, and the guard that no ReLU mask hangs on rounding."""
+    N, C, H, W = shape
+    first = shape == BN_BWD_SHAPE  # (keeps the data and the checks it always had)
+    x = quant(rnd((N, C, H, W), 1 if first else BN_BWD_SEED[shape, dtype]) * 1.5 + 0.3, dtype)
+    gamma = torch.rand(C) if first else torch.rand(C, generator=torch.Generator().manual_seed(7))
+    gamma, beta = (gamma + 0.5).requires_grad_(), rnd((C,), 3, 0.2).requires_grad_()
     xr = x.double().requires_grad_()
     y = TF.batch_norm(xr, None, None, gamma.double(), beta.double(), True, 0.1, 1e-5)
+    if not first:
+        margin = y.detach().abs().min().item()
+        assert margin > 1e-5, "smallest |BN(x)| of the reference %.3e" % margin
     if relu:
         y = torch.relu(y)
     mul = (torch.rand(N, C) > 0.3).double() / 0.7
     g = quant(rnd((N, C, H, W), 5), dtype)
     (y * mul.view(N, C, 1, 1)).backward(g.double())
+    return x, gamma, beta, xr, mul, g
+
+
+# The ids keep the first shape's test names, and with them the seed conftest.py derives from a
+# test's name for torch's global generator (its gamma and every channel mask are drawn from it).
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("relu,shape", [pytest.param(False, BN_BWD_SHAPE, id="False"),
+                                        pytest.param(True, BN_BWD_SHAPE, id="True"),
+                                        pytest.param(False, BN_BWD_SMALL_728, id="False-728"),
+                                        pytest.param(True, BN_BWD_SMALL_728, id="True-728"),
+                                        pytest.param(False, BN_BWD_ROW, id="False-728-rowtile"),
+                                        pytest.param(True, BN_BWD_ROW, id="True-728-rowtile")])
+def test_bn_backward_matches_autograd(dtype, relu, shape, monkeypatch):
+    """relu(BN_train(x)) * mask consumed with gradient g: dx, dgamma, dbeta vs torch autograd"""
+    N, C, H, W = shape
+    x, gamma, beta, xr, mul, g = _bn_backward_reference(dtype, relu, shape)
     sums = torch.cat([x.double().sum((0, 2, 3)), (x.double() ** 2).sum((0, 2, 3))]).to(DEV)
     gd, bd = gamma.detach().to(DEV), beta.detach().to(DEV)
     mean, invstd, scale, shift = K().bn_finalize(sums, N * H * W, gd, bd, 1e-5, 0.1, None, None)
     Fm = F()
+    route = []
+    for name in ("bn_bwd_small", "bn_bwd_reduce_partial", "bn_bwd_finalize_p", "bn_bwd_apply"):
+        def spy(*a, _f=getattr(Fm.K, name), _n=name, **kw):
+            route.append(_n)
+            return _f(*a, **kw)
+        monkeypatch.setattr(Fm.K, name, spy)
     bn = Fm.BNState(gd, bd, mean, invstd, scale, shift, float(N * H * W), True)
     dx, dgamma, dbeta = Fm.bn_input_backward(to_dev_nhwc(g, dtype), to_dev_nhwc(x, dtype), bn, relu,
                                              mul.float().to(DEV))
+    assert route == (["bn_bwd_reduce_partial", "bn_bwd_finalize_p", "bn_bwd_apply"]
+                     if N * H * W > K().SMALL_BN_ROWS else ["bn_bwd_small"]), route
+    assert (shape == BN_BWD_ROW) == (len(route) == 3)
     assert_close(to_cpu_nchw(dx), xr.grad, dtype, "bn dx", fac=3)
     assert_close(dgamma.cpu(), gamma.grad, torch.float32, "dgamma", fac=20)
     assert_close(dbeta.cpu(), beta.grad, torch.float32, "dbeta", fac=20)

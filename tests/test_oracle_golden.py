@@ -4,9 +4,19 @@ import json
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import synth, torch_ref
+
+
+@pytest.fixture(autouse=True)
+def _fixture_thread_count():
+    """The thread count tests/conftest.py sets.  The full-size GPU tests ask for 32 threads and leave
+    them behind when the whole suite runs in one process; at 32 the CPU oracle's fp32 logits move by
+    more than the 1e-4 these fixtures allow (measured: reproduced at 8 and at 16 threads, not at
+    32), so the outcome of these tests depended on what ran before them."""
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
 
 
 def _load_state(golden_dir):

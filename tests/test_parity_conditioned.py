@@ -127,6 +127,10 @@ def _maxrel(a, b):
 # ----------------------------------------------------------------------------- CPU: the fixture
 @pytest.mark.parametrize("tag", list(CASES))
 def test_conditioned_fixture_is_reproduced_by_the_oracle_and_is_conditioned(tag):
+    # (the thread count of conftest.py: the full-size tests before this one in a whole-suite run
+    # leave 32 behind, and at 32 threads the CPU oracle misses the fixture's bars — measured:
+    # reproduced at 8 and at 16 threads, not at 32)
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
     g = _fixture(tag)
     c3, c4, c5, c6 = g["conditioning"]
     assert c3 <= 1e-5 and c4 <= 1.5e-4 and c5 <= 1e-2 and c6 <= 0.1, g["conditioning"]
