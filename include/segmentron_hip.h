@@ -98,7 +98,11 @@ int seg_dwconv3x3_wgrad(int dtype, const void* x, long ldx, int N, int Hi, int W
  *   partial_bn [grid_y][2][C] : (sum g, sum g*x_raw) for seg_bn_bwd_finalize_p (nullable)
  * x is the forward input (raw tensor + prologue), w9c the FORWARD taps (w_layout as above, bit 1
  * unused).  grid_y from seg_dwconv_grid_y(dtype, C, N, H, W, 1, dil, 1).  dil <= 2: LDS-tiled
- * kernel with a tile software pipeline (csrc/dwconv_tiled.hip); wider dilations: strip kernel. */
+ * kernel with a tile software pipeline (csrc/dwconv_tiled.hip); wider dilations: strip kernel.
+ * C and the three pitches must be multiples of 4.  The LDS-tiled kernel (dil 2) wants all of them
+ * multiples of 8 in bf16; the row-chain kernel (dil 3..64, csrc/dwconv_row.hip), which stages dy
+ * with 16-byte vectors, wants C and lddy multiples of 8 in bf16 — a bf16 C = 4 (mod 8) there is
+ * an error, not an over-read.  The sliding (dil 1) and strip (dil > 64) kernels take 4. */
 int seg_dwconv3x3_bwd_fused(int dtype, const void* dy, long lddy, const void* x, long ldx, int N,
                             int H, int W, int C, const float* w9c, int w_layout, int dil,
                             int pro_mode, const float* pro_scale, const float* pro_shift, void* g,

@@ -644,9 +644,16 @@ extern "C" int seg_dwconv3x3_bwd_fused(int dtype, const void* dy, long lddy, con
                                (hipStream_t)stream);
   }
   SEG_REQUIRE(w_layout == 0, "dwconv3x3_bwd_fused: the strip kernel takes tap-major weights");
-  if (g_dw_row && dw_row_supported(1, dil))
+  if (g_dw_row && dw_row_supported(1, dil)) {
+    // the row-chain kernel stages dy with 16-byte vectors (8 bf16 channels): a bf16 C = 4 (mod 8)
+    // would read four channels past C (past the tensor on the last pixel), at 8-byte alignment
+    const int tvec = dtype == DT_BF16 ? 8 : 4;
+    // (x and g move as 4-channel vectors: the common check above is all their pitches need)
+    SEG_REQUIRE(C % tvec == 0 && lddy % tvec == 0,
+                "dwconv3x3_bwd_fused: C/lddy must be multiples of %d", tvec);
     return launch_dw_row_bwd(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, dil, pro_mode, pro_scale,
                              pro_shift, g, ldg, partial_w, partial_bn, grid_y, (hipStream_t)stream);
+  }
   DwBwdArgs a;
   a.dy = dy; a.x = x; a.g = g; a.w = w9c; a.pro_scale = pro_scale; a.pro_shift = pro_shift;
   a.partial_w = partial_w; a.partial_bn = partial_bn;

@@ -246,13 +246,25 @@ def dwconv(x, w9c, stride, dil, pro=None, out=None, want_stats=False):
     return out, partial
 
 
-def dwconv_dgrad(dy, w9c, stride, dil, in_hw, flipped=True):
+def _dw_grad_out(out, N, H, W, C, like):
+    """-> (g, ldg): a fresh [N,H,W,C] gradient tensor, or the caller's `out` (an NHWC view of that
+    shape and dtype, possibly a channel slice of a wider buffer)."""
+    if out is None:
+        return torch.empty((N, H, W, C), dtype=like.dtype, device=like.device), C
+    if tuple(out.shape) != (N, H, W, C) or out.dtype != like.dtype:
+        raise RuntimeError("out: expected %s %s, got %s %s"
+                           % ((N, H, W, C), like.dtype, tuple(out.shape), out.dtype))
+    return out, nhwc(out)[4]
+
+
+def dwconv_dgrad(dy, w9c, stride, dil, in_hw, flipped=True, out=None):
     """stride 1: the forward correlation with the taps reversed.  `w9c` is either the
     [C,1,3,3] parameter (reversed inside the kernel), or a tap-major [9, C] packing that is
-    ALREADY reversed (`flipped=True`, pack_dw_weight(..., flipped=True)) / not yet."""
+    ALREADY reversed (`flipped=True`, pack_dw_weight(..., flipped=True)) / not yet.
+    out: write dx there (an NHWC view, e.g. a channel slice) instead of a fresh tensor."""
     N, Ho, Wo, C, lddy = nhwc(dy)
     Hi, Wi = in_hw
-    dx = torch.empty((N, Hi, Wi, C), dtype=dy.dtype, device=dy.device)
+    dx, lddx = _dw_grad_out(out, N, Hi, Wi, C, dy)
     gy = LIB.query("seg_dwconv_grid_y", _DT[dy.dtype], C, N, Hi, Wi, stride, dil, 0)
     if stride == 1:
         if w9c.dim() == 4:
@@ -262,10 +274,10 @@ def dwconv_dgrad(dy, w9c, stride, dil, in_hw, flipped=True):
         else:
             w, layout = (w9c if flipped else w9c.flip(0).contiguous()), 0
         LIB.call("seg_dwconv3x3", _DT[dy.dtype], 0, _p(dy), lddy, N, Ho, Wo, C, _p(w), layout, 1,
-                 dil, PRO_NONE, 0, 0, _p(dx), C, Hi, Wi, 0, gy, _stream())
+                 dil, PRO_NONE, 0, 0, _p(dx), lddx, Hi, Wi, 0, gy, _stream())
     else:
         LIB.call("seg_dwconv3x3", _DT[dy.dtype], 1, _p(dy), lddy, N, Ho, Wo, C, _p(w9c), 0, stride,
-                 dil, PRO_NONE, 0, 0, _p(dx), C, Hi, Wi, 0, gy, _stream())
+                 dil, PRO_NONE, 0, 0, _p(dx), lddx, Hi, Wi, 0, gy, _stream())
     return dx
 
 
@@ -307,14 +319,15 @@ def dwconv_bwd_fused_add_ok(x, dil):
 
 
 def dwconv_bwd_fused(x, dy, w, dil, pro=None, want_bn=False, torch_layout=False, raw_dw=False,
-                     res=None):
+                     res=None, out=None):
     """stride-1 depthwise backward in one pass: returns (g masked by the prologue's ReLU,
     dW fp32 [9, C] (or [C,1,3,3] with torch_layout), bn_partial fp32 [gy, 2C] | None).
-    w: tap-major [9, C] or (dil <= 2) the [C,1,3,3] parameter itself."""
+    w: tap-major [9, C] or (dil <= 2) the [C,1,3,3] parameter itself.
+    out: write g there (an NHWC view, e.g. a channel slice) instead of a fresh tensor."""
     N, H, W, C, ldx = nhwc(x)
     lddy = nhwc(dy)[4]
     mode, ps, pt = _pro(pro)
-    g = torch.empty((N, H, W, C), dtype=x.dtype, device=x.device)
+    g, ldg = _dw_grad_out(out, N, H, W, C, x)
     tiled = dw_tiled(1, dil)
     layout = 1 if w.dim() == 4 else 0
     if layout and not tiled:
@@ -325,11 +338,11 @@ def dwconv_bwd_fused(x, dy, w, dil, pro=None, want_bn=False, torch_layout=False,
     if res is not None:  # g = masked dgrad + res (the other gradient of a forked activation)
         assert dil == 1 and tuple(res.shape) == (N, H, W, C) and res.dtype == x.dtype
         LIB.call("seg_dwconv3x3_bwd_fused_add", _DT[x.dtype], _p(dy), lddy, _p(x), ldx, N, H, W,
-                 C, _p(w), layout, mode, _p(ps), _p(pt), _p(res), nhwc(res)[4], _p(g), C, _p(pw),
+                 C, _p(w), layout, mode, _p(ps), _p(pt), _p(res), nhwc(res)[4], _p(g), ldg, _p(pw),
                  _p(pb), gy, _stream())
     else:
         LIB.call("seg_dwconv3x3_bwd_fused", _DT[x.dtype], _p(dy), lddy, _p(x), ldx, N, H, W, C,
-                 _p(w), layout, dil, mode, _p(ps), _p(pt), _p(g), C, _p(pw), _p(pb), gy, _stream())
+                 _p(w), layout, dil, mode, _p(ps), _p(pt), _p(g), ldg, _p(pw), _p(pb), gy, _stream())
     if raw_dw:  # the caller reduces pw together with pb (dw_bwd_finalize)
         return g, pw, pb
     if torch_layout:
@@ -339,20 +352,20 @@ def dwconv_bwd_fused(x, dy, w, dil, pro=None, want_bn=False, torch_layout=False,
     return g, colsum(pw, f64=False).view(9, C), pb
 
 
-def dwconv_bwd_fused_s2(x, dy, w, pro=None, want_bn=False, raw_dw=False):
+def dwconv_bwd_fused_s2(x, dy, w, pro=None, want_bn=False, raw_dw=False, out=None):
     """stride-2 (pad 1, dil 1) depthwise backward in one pass over dy and x: returns (g masked by
     the prologue's ReLU, dW fp32 [C,1,3,3], bn_partial fp32 [gy, 2C] | None).  w: the [C,1,3,3]
-    parameter."""
+    parameter.  out: write g there (an NHWC view) instead of a fresh tensor."""
     N, H, W, C, ldx = nhwc(x)
     Nd, Ho, Wo, Cd, lddy = nhwc(dy)
     assert (Nd, Ho, Wo, Cd) == (N, (H + 1) // 2, (W + 1) // 2, C) and tuple(w.shape) == (C, 1, 3, 3)
     mode, ps, pt = _pro(pro)
-    g = torch.empty((N, H, W, C), dtype=x.dtype, device=x.device)
+    g, ldg = _dw_grad_out(out, N, H, W, C, x)
     gy = LIB.query("seg_dwconv3x3_s2_grid_y", C, N, H, W)
     pw = torch.empty((gy, 9 * C), dtype=torch.float32, device=x.device)
     pb = torch.empty((gy, 2 * C), dtype=torch.float32, device=x.device) if want_bn else None
     LIB.call("seg_dwconv3x3_s2_bwd_fused", _DT[x.dtype], _p(dy), lddy, _p(x), ldx, N, H, W, C,
-             _p(w), mode, _p(ps), _p(pt), _p(g), C, _p(pw), _p(pb), gy, _stream())
+             _p(w), mode, _p(ps), _p(pt), _p(g), ldg, _p(pw), _p(pb), gy, _stream())
     if raw_dw:
         return g, pw, pb
     dW = torch.empty((C, 1, 3, 3), dtype=torch.float32, device=x.device)
