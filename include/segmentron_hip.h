@@ -76,13 +76,17 @@ int seg_conv_gemm_wgrad_splits(int dtype, int N, int Ho, int Wo, int C, int O, i
  * stride 1 / dilation <= 2 only), bit 1 = taps read reversed (stride-1 data gradient = forward
  * correlation with flipped taps).  mode 0: forward (x -> y).  mode 1: data gradient
  * (x = dy with geometry N,Hi,Wi; y = dx with geometry Ho,Wo; same w9c, stride, dil).
- * stat_partial (forward only, nullable): [grid_y][2][C].  grid_y from seg_dwconv_grid_y. */
+ * stat_partial (forward only, nullable): [grid_y][2][C].  grid_y from seg_dwconv_grid_y.
+ * Which kernel family runs a launch (sliding, LDS-tiled, LDS-tiled stride 2, row-chain, strip),
+ * the channel-vector width and the tap layouts it takes: the table on dw_route, csrc/dwconv.hip. */
 int seg_dwconv3x3(int dtype, int mode, const void* x, long ldx, int N, int Hi, int Wi, int C,
                   const float* w9c, int w_layout, int stride, int dil, int pro_mode,
                   const float* pro_scale, const float* pro_shift, void* y, long ldy, int Ho, int Wo,
                   float* stat_partial, int grid_y, void* stream);
-/* partial rows (= persistent blocks per channel block) of one depthwise launch.
- * kind: 0 forward / data gradient, 1 fused backward, 2 weight gradient */
+/* partial rows (= persistent blocks per channel block) of one depthwise launch, or -1 where there
+ * is no such launch (a non-positive size; C not a positive multiple of the channel vector the
+ * family's geometry counts in).  kind: 0 forward / data gradient, 1 fused backward, 2 weight
+ * gradient */
 int seg_dwconv_grid_y(int dtype, int C, int N, int Ho, int Wo, int stride, int dil, int kind);
 /* partial: fp32 [grid_y][9][C]; column-sum gives dW[9][C];
  * seg_dwconv3x3_wgrad_finalize reduces it straight into torch's [C,1,3,3] layout. */
@@ -97,8 +101,9 @@ int seg_dwconv3x3_wgrad(int dtype, const void* x, long ldx, int N, int Hi, int W
  *   partial_w  [grid_y][9][C] : weight-gradient partials (sum rows -> dW[9][C])
  *   partial_bn [grid_y][2][C] : (sum g, sum g*x_raw) for seg_bn_bwd_finalize_p (nullable)
  * x is the forward input (raw tensor + prologue), w9c the FORWARD taps (w_layout as above, bit 1
- * unused).  grid_y from seg_dwconv_grid_y(dtype, C, N, H, W, 1, dil, 1).  dil <= 2: LDS-tiled
- * kernel with a tile software pipeline (csrc/dwconv_tiled.hip); wider dilations: strip kernel.
+ * unused).  grid_y from seg_dwconv_grid_y(dtype, C, N, H, W, 1, dil, 1).  dil 1: register-sliding
+ * kernel (csrc/dwconv_slide.hip); dil 2: LDS-tiled kernel with a tile software pipeline
+ * (csrc/dwconv_tiled.hip); dil 3..64: row-chain kernel (csrc/dwconv_row.hip); wider: strip kernel.
  * C and the three pitches must be multiples of 4.  The LDS-tiled kernel (dil 2) wants all of them
  * multiples of 8 in bf16; the row-chain kernel (dil 3..64, csrc/dwconv_row.hip), which stages dy
  * with 16-byte vectors, wants C and lddy multiples of 8 in bf16 — a bf16 C = 4 (mod 8) there is
@@ -112,7 +117,8 @@ int seg_dwconv3x3_bwd_fused(int dtype, const void* dy, long lddy, const void* x,
  * in the store path: g = relu_mask(x) * dgrad + res — the second gradient of a forked activation
  * (an Xception block input feeds the residual sum and the first separable conv,
  * segmentron/models/backbones/xception.py:36-42), which autograd would add in a separate
- * element-wise pass.  LDS-tiled kernel only: stride 1, dilation 1 (seg_..._add_ok(dil) != 0). */
+ * element-wise pass.  Stride 1, dilation 1 only (seg_..._add_ok(dil) != 0): the register-sliding
+ * kernel.  C and the pitches of dy, x, g: multiples of 8 in bf16, 4 in fp32; ldr: of 4. */
 int seg_dwconv3x3_bwd_fused_add_ok(int dil);
 int seg_dwconv3x3_bwd_fused_add(int dtype, const void* dy, long lddy, const void* x, long ldx, int N,
                                 int H, int W, int C, const float* w9c, int w_layout, int pro_mode,
@@ -409,7 +415,7 @@ int seg_point_ce_bwd(int dtype, const void* x, long ldx, long R, int C, const lo
  * One pass over dy [N,(H+1)/2,(W+1)/2,C] and x [N,H,W,C] (+ prologue): g = masked data gradient,
  * partial_w [grid_y][9][C] (reduce with seg_dwconv3x3_wgrad_finalize), partial_bn [grid_y][2][C]
  * (nullable) = (sum g, sum g*x_raw).  w_c9: torch's [C,1,3,3] fp32.  grid_y from
- * seg_dwconv3x3_s2_grid_y. */
+ * seg_dwconv3x3_s2_grid_y (-1: a non-positive size, or C not a positive multiple of 4). */
 int seg_dwconv3x3_s2_grid_y(int C, int N, int H, int W);
 int seg_dwconv3x3_s2_bwd_fused(int dtype, const void* dy, long lddy, const void* x, long ldx, int N,
                                int H, int W, int C, const float* w_c9, int pro_mode,

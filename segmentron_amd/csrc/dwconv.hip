@@ -16,14 +16,11 @@
 // channel vectors, blockIdx.y the strips (grid-stride), one row of statistics partials per
 // blockIdx.y (deterministic: LDS tree over the strips of a block, fp64 finish in bn_finalize).
 #include "common.h"
-#include "dwconv_tiled.h"
-#include "dwconv_slide.h"
+#include "dwconv.h"
 #include <cstdlib>
 #include <type_traits>
 
 namespace seg {
-
-constexpr bool g_dw_row = true;  // wide dilations on the row-chain kernels (dwconv_row.hip)
 
 constexpr int DW_TW = 4;
 constexpr int DW_THREADS = 256;
@@ -71,9 +68,9 @@ __device__ __forceinline__ void dw_act(float* f, int mode, const float* sc, cons
   }
 }
 
-// Strip kernels: stride 2 and wide dilations (6/12/18) only — every stride-1, dil <= 2 layer runs
-// on the LDS-tiled kernels of dwconv_tiled.hip (the sliding-window fast path these kernels once
-// had for that case is gone with it).
+// Strip kernels: the fallback of dw_route (below) — strided data gradients, strides and dilations no
+// other family takes (stride 2 with dilation, stride 3, dilation > 64); the networks' stride-1
+// layers run on the sliding (dil 1), LDS-tiled (dil 2) and row-chain (dil 6/12/18/...) kernels.
 template <typename T, int MODE>
 __global__ __launch_bounds__(DW_THREADS, 2) void dwconv_kernel(const DwArgs a) {
   using V = Vec<T>;
@@ -458,85 +455,132 @@ static int pick_cvb_log2(int CV) {
   }
   return best;
 }
+// strip launches: blocks along the channel vectors
+static int strip_gx(int CV, int& cvb_log2) {
+  cvb_log2 = pick_cvb_log2(CV);
+  return (CV + (1 << cvb_log2) - 1) >> cvb_log2;
+}
 
-}  // namespace seg
+// The kernel family of a depthwise 3x3 launch: the ONLY statement of that policy in the library
+// (the grid query and every launch entry switch on its result).  v = 8 channels bf16 / 4 fp32.
+//
+//   op                     stride  dil     family      C, pitches % ..   taps
+//   forward (and stride-1  1       1       sliding     v                 torch [C,1,3,3] or [9][C]
+//     data gradient:       1       2       tiled       v                 torch or [9][C]
+//     reversed taps)       2       1       tiled s2    v                 torch or [9][C]
+//                          1       3..64   row-chain   v                 [9][C]
+//                          other           strip       v                 [9][C]
+//   strided data gradient  any     any     strip       v                 [9][C]
+//   fused backward         1       1       sliding     4                 torch or [9][C]
+//                          1       2       tiled       v                 torch or [9][C]
+//                          1       3..64   row-chain   v (C, lddy), 4    [9][C]
+//                          1       > 64    strip       4                 [9][C]
+//   ... with residual      1       1       sliding     v (ldr: 4)        torch or [9][C]
+//   weight gradient        1       1, 2    tiled       v                 -
+//                          other           strip       v                 -
+//
+// The sliding and row-chain families need C % 4 == 0, which every entry checks before it launches:
+// a dilation-1 launch never reaches the tiled family.  (The stride-2 fused backward has its own
+// entry point and kernel, dwconv_s2.hip: C and pitches % 4, torch taps.)
+DwRoute dw_route(DwOp op, int dtype, int C, int stride, int dil) {
+  const int v = dtype == DT_BF16 ? 8 : 4;
+  const bool s1 = stride == 1 && op != DW_OP_DGRAD;
+  DwFamily f = DW_STRIP;
+  if (s1 && dil == 1 && C % 4 == 0 && op != DW_OP_WGRAD) f = DW_SLIDE;
+  else if (s1 && (dil == 1 || dil == 2)) f = DW_TILED;
+  else if (op == DW_OP_FWD && stride == 2 && dil == 1) f = DW_TILED_S2;
+  else if (s1 && dil > 2 && dil <= 64 && C % 4 == 0 && op != DW_OP_WGRAD) f = DW_ROW;
+  const bool narrow = op == DW_OP_BWD && (f == DW_SLIDE || f == DW_STRIP);  // HVec: 4 channels
+  return {f, narrow ? 4 : v, f == DW_SLIDE || f == DW_TILED || f == DW_TILED_S2};
+}
 
-// Number of partial rows / persistent blocks per channel block for one depthwise launch.
-// kind: 0 forward / data gradient, 1 fused backward, 2 weight gradient (the LDS-tiled kernels size
-// them differently; the strip kernels — stride 2, dilation > 2 — share one geometry).
-extern "C" int seg_dwconv_grid_y(int dtype, int C, int N, int Ho, int Wo, int stride, int dil,
-                                 int kind) {
-  using namespace seg;
-  const int tiled_stride = kind == 0 ? stride : 1;  // kinds 1/2 describe a stride-1 layer's backward
-  // r06: stride 1 / dilation 1 forward and fused backward on the register-sliding kernels
-  if ((kind == 0 || kind == 1) && dw_slide_supported(stride, dil, C))
-    return dw_slide_rows(C, N, Ho, Wo);
-  if ((kind == 0 || stride == 1) && dw_tiled_supported(tiled_stride, dil))
-    return dw_tiled_grid_y(dtype, C, N, Ho, Wo, kind);
-  if (kind == 0 && stride == 2 && dil == 1)  // LDS-tiled stride-2 forward
-    return dw_tiled_s2_grid_y(dtype, C, N, Ho, Wo);
-  if (g_dw_row && (kind == 0 || kind == 1) && dw_row_supported(stride, dil) && C % 4 == 0)
-    return dw_row_grid_y(dtype, C, N, Ho, Wo, dil);  // stride 1: Ho x Wo is the input size too
-  const int vec = dtype == DT_BF16 ? 8 : 4;
-  const int CV = C / vec;
-  const int l = pick_cvb_log2(CV);
+int dw_route_grid_y(DwRoute r, DwOp op, int dtype, int C, int N, int Ho, int Wo, int dil) {
+  const int v = dtype == DT_BF16 ? 8 : 4;
+  const bool fused = op == DW_OP_BWD || op == DW_OP_BWD_ADD;
+  // the channel vector the family's geometry counts in
+  const int gvec = (fused || r.family == DW_SLIDE || r.family == DW_ROW) ? 4 : v;
+  if (N < 1 || Ho < 1 || Wo < 1 || C < gvec || C % gvec != 0) return -1;
+  switch (r.family) {
+    case DW_SLIDE: return dw_slide_rows(C, N, Ho, Wo);
+    case DW_TILED:
+      return dw_tiled_grid_y(dtype, C, N, Ho, Wo, fused ? 1 : op == DW_OP_WGRAD ? 2 : 0);
+    case DW_TILED_S2: return dw_tiled_s2_grid_y(dtype, C, N, Ho, Wo);
+    case DW_ROW: return dw_row_grid_y(dtype, C, N, Ho, Wo, dil);  // stride 1: the input size too
+    case DW_STRIP: break;
+  }
+  if (C < v) return -1;  // (the strip geometry counts whole v-channel vectors for every op)
+  int l;
+  const int gx = strip_gx(C / v, l);
   const int spb = DW_THREADS >> l;
   const long strips = (long)N * Ho * ((Wo + DW_TW - 1) / DW_TW);
-  const int gx = (CV + (1 << l) - 1) >> l;
   long gy = (strips + spb - 1) / spb;
   long cap = 1536 / gx;  // ~6 blocks per CU; bounds the number of partial rows
   if (cap < 1) cap = 1;
   if (gy > cap) gy = cap;
   return (int)gy;
 }
+
+}  // namespace seg
+
+// Number of partial rows / persistent blocks per channel block for one depthwise launch, or -1
+// where there is no such launch (non-positive sizes, C not made of the family's channel vectors).
+// kind: 0 forward / data gradient, 1 fused backward, 2 weight gradient.
+extern "C" int seg_dwconv_grid_y(int dtype, int C, int N, int Ho, int Wo, int stride, int dil,
+                                 int kind) {
+  using namespace seg;
+  static const DwOp ops[3] = {DW_OP_FWD, DW_OP_BWD, DW_OP_WGRAD};
+  if ((dtype != DT_F32 && dtype != DT_BF16) || kind < 0 || kind > 2 || stride < 1 || dil < 1)
+    return -1;
+  return dw_route_grid_y(dw_route(ops[kind], dtype, C, stride, dil), ops[kind], dtype, C, N, Ho, Wo,
+                         dil);
+}
+
 extern "C" int seg_dwconv3x3(int dtype, int mode, const void* x, long ldx, int N, int Hi, int Wi,
                              int C, const float* w9c, int w_layout, int stride, int dil, int pro_mode,
                              const float* pro_scale, const float* pro_shift, void* y, long ldy,
                              int Ho, int Wo, float* stat_partial, int grid_y, void* stream) {
   using namespace seg;
-  const int vec = dtype == DT_BF16 ? 8 : 4;
   SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "dwconv3x3: bad dtype %d", dtype);
+  const DwRoute r = dw_route(mode == MODE_FWD ? DW_OP_FWD : DW_OP_DGRAD, dtype, C, stride, dil);
+  const int vec = r.vec;
   SEG_REQUIRE(C % vec == 0 && ldx % vec == 0 && ldy % vec == 0,
               "dwconv3x3: C/ldx/ldy must be multiples of %d", vec);
   SEG_REQUIRE(((pro_mode & PRO_AFFINE) == 0) || (pro_scale && pro_shift),
               "dwconv3x3: affine prologue without scale/shift");
   SEG_REQUIRE(mode == MODE_FWD || stat_partial == nullptr, "dwconv3x3: stats only in forward");
   SEG_REQUIRE(grid_y >= 1, "dwconv3x3: grid_y must be >= 1");
-  if (mode == MODE_FWD && dw_slide_supported(stride, dil, C)) {
-    SEG_REQUIRE(Ho == Hi && Wo == Wi, "dwconv3x3: stride 1 keeps the size");
-    return launch_dw_slide_fwd(dtype, x, ldx, N, Hi, Wi, C, w9c, w_layout, pro_mode, pro_scale,
-                               pro_shift, y, ldy, stat_partial, grid_y, (hipStream_t)stream);
-  }
-  if (mode == MODE_FWD && dw_tiled_supported(stride, dil)) {  // incl. stride-1 dgrad (flipped taps)
-    SEG_REQUIRE(Ho == Hi && Wo == Wi, "dwconv3x3: stride 1 keeps the size");
-    return launch_dw_tiled(dtype, x, ldx, N, Hi, Wi, C, w9c, w_layout, dil, pro_mode, pro_scale,
-                           pro_shift, y, ldy, stat_partial, grid_y, (hipStream_t)stream);
-  }
-  if (mode == MODE_FWD && stride == 2 && dil == 1) {  // LDS-tiled stride-2 forward
-    SEG_REQUIRE(Ho == (Hi + 1) / 2 && Wo == (Wi + 1) / 2, "dwconv3x3: stride-2 output size");
-    SEG_REQUIRE((long)N * Hi * Wi < (1L << 31), "dwconv3x3: tensor exceeds 32-bit pixel offsets");
-    return launch_dw_tiled_s2(dtype, x, ldx, N, Hi, Wi, C, w9c, w_layout, pro_mode, pro_scale,
-                              pro_shift, y, ldy, stat_partial, grid_y, (hipStream_t)stream);
-  }
-  SEG_REQUIRE(w_layout == 0, "dwconv3x3: the strip kernels take tap-major [9][C] weights");
-  if (g_dw_row && mode == MODE_FWD && dw_row_supported(stride, dil) && C % 4 == 0) {
-    SEG_REQUIRE(Ho == Hi && Wo == Wi, "dwconv3x3: stride 1 keeps the size");
-    return launch_dw_row_fwd(dtype, x, ldx, N, Hi, Wi, C, w9c, dil, pro_mode, pro_scale, pro_shift,
-                             y, ldy, stat_partial, grid_y, (hipStream_t)stream);
+  SEG_REQUIRE(r.torch_taps || w_layout == 0,
+              "dwconv3x3: the row-chain and strip kernels take tap-major [9][C] weights");
+  hipStream_t st = (hipStream_t)stream;
+  switch (r.family) {
+    case DW_SLIDE:
+    case DW_TILED:  // incl. the stride-1 data gradient (reversed taps)
+    case DW_ROW:
+      SEG_REQUIRE(Ho == Hi && Wo == Wi, "dwconv3x3: stride 1 keeps the size");
+      if (r.family == DW_SLIDE)
+        return launch_dw_slide_fwd(dtype, x, ldx, N, Hi, Wi, C, w9c, w_layout, pro_mode, pro_scale,
+                                   pro_shift, y, ldy, stat_partial, grid_y, st);
+      if (r.family == DW_TILED)
+        return launch_dw_tiled(dtype, x, ldx, N, Hi, Wi, C, w9c, w_layout, dil, pro_mode, pro_scale,
+                               pro_shift, y, ldy, stat_partial, grid_y, st);
+      return launch_dw_row_fwd(dtype, x, ldx, N, Hi, Wi, C, w9c, dil, pro_mode, pro_scale, pro_shift,
+                               y, ldy, stat_partial, grid_y, st);
+    case DW_TILED_S2:
+      SEG_REQUIRE(Ho == (Hi + 1) / 2 && Wo == (Wi + 1) / 2, "dwconv3x3: stride-2 output size");
+      SEG_REQUIRE((long)N * Hi * Wi < (1L << 31), "dwconv3x3: tensor exceeds 32-bit pixel offsets");
+      return launch_dw_tiled_s2(dtype, x, ldx, N, Hi, Wi, C, w9c, w_layout, pro_mode, pro_scale,
+                                pro_shift, y, ldy, stat_partial, grid_y, st);
+    case DW_STRIP: break;
   }
   DwArgs a;
   a.x = x; a.w = w9c; a.y = y; a.pro_scale = pro_scale; a.pro_shift = pro_shift;
   a.stat_partial = stat_partial; a.ldx = ldx; a.ldy = ldy;
   a.N = N; a.Hi = Hi; a.Wi = Wi; a.C = C; a.Ho = Ho; a.Wo = Wo;
   a.stride = stride; a.pad = dil; a.dil = dil; a.pro_mode = pro_mode;
-  const int kvec = vec;  // channels per thread
-  a.CV = C / kvec; a.cvb_log2 = pick_cvb_log2(a.CV);
+  a.CV = C / vec;  // vec channels per thread
   a.strips = (long)N * Ho * ((Wo + DW_TW - 1) / DW_TW);
-  const int gx = (a.CV + (1 << a.cvb_log2) - 1) >> a.cvb_log2;
-  SEG_REQUIRE(grid_y >= 1, "dwconv3x3: grid_y must be >= 1");
-  const dim3 grid(gx, grid_y);
-  const size_t lds = stat_partial ? (size_t)DW_THREADS * 2 * kvec * sizeof(float) : 0;
-  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(strip_gx(a.CV, a.cvb_log2), grid_y);
+  const size_t lds = stat_partial ? (size_t)DW_THREADS * 2 * vec * sizeof(float) : 0;
   SEG_REQUIRE(a.strips < (1L << 31), "dwconv3x3: too many strips");
   SEG_REQUIRE((long)N * Hi * Wi * ldx < (1L << 31), "dwconv3x3: tensor exceeds 32-bit offsets");
 #define SEG_DW_LAUNCH(TT, MM) \
@@ -556,27 +600,26 @@ extern "C" int seg_dwconv3x3_wgrad(int dtype, const void* x, long ldx, int N, in
                                    const float* pro_shift, float* partial, int grid_y,
                                    void* stream) {
   using namespace seg;
-  const int vec = dtype == DT_BF16 ? 8 : 4;
   SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "dwconv3x3_wgrad: bad dtype %d", dtype);
+  const DwRoute r = dw_route(DW_OP_WGRAD, dtype, C, stride, dil);
+  const int vec = r.vec;
   SEG_REQUIRE(C % vec == 0 && ldx % vec == 0 && lddy % vec == 0,
               "dwconv3x3_wgrad: C/ldx/lddy must be multiples of %d", vec);
   SEG_REQUIRE(grid_y >= 1, "dwconv3x3_wgrad: grid_y must be >= 1");
-  if (dw_tiled_supported(stride, dil)) {
+  hipStream_t st = (hipStream_t)stream;
+  if (r.family == DW_TILED) {
     SEG_REQUIRE(Ho == Hi && Wo == Wi, "dwconv3x3_wgrad: stride 1 keeps the size");
     return launch_dw_wgrad_tiled(dtype, x, ldx, N, Hi, Wi, C, dy, lddy, dil, pro_mode, pro_scale,
-                                 pro_shift, partial, grid_y, (hipStream_t)stream);
+                                 pro_shift, partial, grid_y, st);
   }
   DwWgradArgs a;
   a.x = x; a.dy = dy; a.partial = partial; a.pro_scale = pro_scale; a.pro_shift = pro_shift;
   a.ldx = ldx; a.lddy = lddy; a.N = N; a.Hi = Hi; a.Wi = Wi; a.C = C; a.Ho = Ho; a.Wo = Wo;
   a.stride = stride; a.pad = dil; a.dil = dil; a.pro_mode = pro_mode;
-  a.CV = C / vec; a.cvb_log2 = pick_cvb_log2(a.CV);
+  a.CV = C / vec;
   a.strips = (long)N * Ho * ((Wo + DW_TW - 1) / DW_TW);
-  const int gx = (a.CV + (1 << a.cvb_log2) - 1) >> a.cvb_log2;
-  SEG_REQUIRE(grid_y >= 1, "dwconv3x3_wgrad: grid_y must be >= 1");
-  const dim3 grid(gx, grid_y);
+  const dim3 grid(strip_gx(a.CV, a.cvb_log2), grid_y);
   const size_t lds = (size_t)DW_THREADS * 3 * vec * sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
   SEG_REQUIRE(a.strips < (1L << 31), "dwconv3x3_wgrad: too many strips");
   if (dtype == DT_BF16)
     hipLaunchKernelGGL((dwconv_wgrad_kernel<bf16_t>), grid, dim3(DW_THREADS), lds, st, a);
@@ -588,9 +631,63 @@ extern "C" int seg_dwconv3x3_wgrad(int dtype, const void* x, long ldx, int N, in
 // Fused stride-1 backward: g = relu_mask(x) * dgrad(dy), partial_w [grid_y][9][C],
 // partial_bn [grid_y][2][C] = (sum g, sum g*x_raw) (nullable).  x is the forward input (raw tensor
 // + prologue), w9c the forward taps (not reversed).
-// The same with a tensor `res` ([N,H,W,C], pitch ldr, element type of g) added to the masked data
-// gradient in the store path: g = relu_mask(x) * dgrad + res.  LDS-tiled kernel only (stride 1,
-// dilation 1) — the caller falls back to a separate add otherwise (seg_dwconv3x3_bwd_fused_add_ok).
+// With `res` ([N,H,W,C], pitch ldr, element type of g; the _add entry): that tensor is added to the
+// masked data gradient in the store path, g = relu_mask(x) * dgrad + res.  Dilation 1 only — the
+// caller does a separate add otherwise (seg_dwconv3x3_bwd_fused_add_ok).
+namespace seg {
+static int dw_bwd_fused(const char* name, int dtype, const void* dy, long lddy, const void* x,
+                        long ldx, int N, int H, int W, int C, const float* w9c, int w_layout,
+                        int dil, int pro_mode, const float* pro_scale, const float* pro_shift,
+                        const void* res, long ldr, void* g, long ldg, float* partial_w,
+                        float* partial_bn, int grid_y, hipStream_t st) {
+  const int vec = 4;  // HVec: 4 channels per thread in both element types
+  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "%s: bad dtype %d", name, dtype);
+  const DwRoute r = dw_route(res ? DW_OP_BWD_ADD : DW_OP_BWD, dtype, C, 1, dil);
+  SEG_REQUIRE(C % vec == 0 && ldx % vec == 0 && lddy % vec == 0 && ldg % vec == 0 && ldr % vec == 0,
+              "%s: C/ld must be multiples of %d", name, vec);
+  SEG_REQUIRE(((pro_mode & PRO_AFFINE) == 0) || (pro_scale && pro_shift),
+              "%s: affine prologue without scale/shift", name);
+  SEG_REQUIRE(grid_y >= 1 && partial_w != nullptr, "%s: bad grid/partials", name);
+  SEG_REQUIRE(r.torch_taps || w_layout == 0,
+              "%s: the row-chain and strip kernels take tap-major [9][C] weights", name);
+  // the row-chain kernel stages dy with 16-byte vectors (8 bf16 channels): a bf16 C = 4 (mod 8)
+  // would read four channels past C (past the tensor on the last pixel), at 8-byte alignment;
+  // its x and g move as 4-channel vectors: the common check above is all their pitches need
+  SEG_REQUIRE(C % r.vec == 0 && lddy % r.vec == 0 &&
+                  (r.family == DW_ROW || (ldx % r.vec == 0 && ldg % r.vec == 0)),
+              "%s: C/ld must be multiples of %d", name, r.vec);
+  switch (r.family) {
+    case DW_SLIDE:
+      return launch_dw_slide_bwd(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, w_layout, pro_mode,
+                                 pro_scale, pro_shift, g, ldg, partial_w, partial_bn, grid_y, st,
+                                 res, ldr);
+    case DW_TILED:
+      return launch_dw_bwd_tiled(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, w_layout, dil, pro_mode,
+                                 pro_scale, pro_shift, g, ldg, partial_w, partial_bn, grid_y, st,
+                                 res, ldr);
+    case DW_ROW:
+      return launch_dw_row_bwd(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, dil, pro_mode, pro_scale,
+                               pro_shift, g, ldg, partial_w, partial_bn, grid_y, st);
+    default: break;
+  }
+  DwBwdArgs a;
+  a.dy = dy; a.x = x; a.g = g; a.w = w9c; a.pro_scale = pro_scale; a.pro_shift = pro_shift;
+  a.partial_w = partial_w; a.partial_bn = partial_bn;
+  a.lddy = lddy; a.ldx = ldx; a.ldg = ldg; a.N = N; a.H = H; a.W = W; a.C = C; a.dil = dil;
+  a.pro_mode = pro_mode; a.CV = C / vec;
+  a.strips = (long)N * H * ((W + DW_TW - 1) / DW_TW);
+  SEG_REQUIRE(a.strips < (1L << 31), "%s: too many strips", name);
+  SEG_REQUIRE((long)N * H * W * lddy < (1L << 31), "%s: 32-bit offsets", name);
+  const dim3 grid(strip_gx(a.CV, a.cvb_log2), grid_y);
+  const size_t lds = (size_t)DW_THREADS * 3 * vec * sizeof(float);
+  if (dtype == DT_BF16)
+    hipLaunchKernelGGL((dwconv_bwd_fused_kernel<bf16_t>), grid, dim3(DW_THREADS), lds, st, a);
+  else
+    hipLaunchKernelGGL((dwconv_bwd_fused_kernel<float>), grid, dim3(DW_THREADS), lds, st, a);
+  return check_launch(name);
+}
+}  // namespace seg
+
 extern "C" int seg_dwconv3x3_bwd_fused_add_ok(int dil) { return dil == 1 ? 1 : 0; }
 
 extern "C" int seg_dwconv3x3_bwd_fused_add(int dtype, const void* dy, long lddy, const void* x,
@@ -599,22 +696,11 @@ extern "C" int seg_dwconv3x3_bwd_fused_add(int dtype, const void* dy, long lddy,
                                            const float* pro_shift, const void* res, long ldr,
                                            void* g, long ldg, float* partial_w, float* partial_bn,
                                            int grid_y, void* stream) {
-  using namespace seg;
-  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "dwconv3x3_bwd_fused_add: bad dtype %d", dtype);
-  const int tvec = dtype == DT_BF16 ? 8 : 4;
-  SEG_REQUIRE(C % tvec == 0 && ldx % tvec == 0 && lddy % tvec == 0 && ldg % tvec == 0 &&
-                  ldr % 4 == 0 && res != nullptr,
-              "dwconv3x3_bwd_fused_add: C/ld must be multiples of %d, res non-null", tvec);
-  SEG_REQUIRE(((pro_mode & PRO_AFFINE) == 0) || (pro_scale && pro_shift),
-              "dwconv3x3_bwd_fused_add: affine prologue without scale/shift");
-  SEG_REQUIRE(grid_y >= 1 && partial_w != nullptr, "dwconv3x3_bwd_fused_add: bad grid/partials");
-  if (dw_slide_supported(1, 1, C))
-    return launch_dw_slide_bwd(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, w_layout, pro_mode,
-                               pro_scale, pro_shift, g, ldg, partial_w, partial_bn, grid_y,
-                               (hipStream_t)stream, res, ldr);
-  return launch_dw_bwd_tiled(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, w_layout, 1, pro_mode,
-                             pro_scale, pro_shift, g, ldg, partial_w, partial_bn, grid_y,
-                             (hipStream_t)stream, res, ldr);
+  SEG_REQUIRE(res != nullptr, "dwconv3x3_bwd_fused_add: C/ld must be multiples of %d, res non-null",
+              dtype == seg::DT_BF16 ? 8 : 4);
+  return seg::dw_bwd_fused("dwconv3x3_bwd_fused_add", dtype, dy, lddy, x, ldx, N, H, W, C, w9c,
+                           w_layout, 1, pro_mode, pro_scale, pro_shift, res, ldr, g, ldg, partial_w,
+                           partial_bn, grid_y, (hipStream_t)stream);
 }
 
 extern "C" int seg_dwconv3x3_bwd_fused(int dtype, const void* dy, long lddy, const void* x,
@@ -623,54 +709,9 @@ extern "C" int seg_dwconv3x3_bwd_fused(int dtype, const void* dy, long lddy, con
                                        const float* pro_shift, void* g, long ldg,
                                        float* partial_w, float* partial_bn, int grid_y,
                                        void* stream) {
-  using namespace seg;
-  const int vec = 4;  // HVec: 4 channels per thread in both element types
-  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "dwconv3x3_bwd_fused: bad dtype %d", dtype);
-  SEG_REQUIRE(C % vec == 0 && ldx % vec == 0 && lddy % vec == 0 && ldg % vec == 0,
-              "dwconv3x3_bwd_fused: C/ld must be multiples of %d", vec);
-  SEG_REQUIRE(((pro_mode & PRO_AFFINE) == 0) || (pro_scale && pro_shift),
-              "dwconv3x3_bwd_fused: affine prologue without scale/shift");
-  SEG_REQUIRE(grid_y >= 1 && partial_w != nullptr, "dwconv3x3_bwd_fused: bad grid/partials");
-  if (dw_slide_supported(1, dil, C))
-    return launch_dw_slide_bwd(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, w_layout, pro_mode,
-                               pro_scale, pro_shift, g, ldg, partial_w, partial_bn, grid_y,
-                               (hipStream_t)stream);
-  if (dw_tiled_supported(1, dil)) {
-    const int tvec = dtype == DT_BF16 ? 8 : 4;
-    SEG_REQUIRE(C % tvec == 0 && ldx % tvec == 0 && lddy % tvec == 0 && ldg % tvec == 0,
-                "dwconv3x3_bwd_fused: C/ld must be multiples of %d", tvec);
-    return launch_dw_bwd_tiled(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, w_layout, dil, pro_mode,
-                               pro_scale, pro_shift, g, ldg, partial_w, partial_bn, grid_y,
-                               (hipStream_t)stream);
-  }
-  SEG_REQUIRE(w_layout == 0, "dwconv3x3_bwd_fused: the strip kernel takes tap-major weights");
-  if (g_dw_row && dw_row_supported(1, dil)) {
-    // the row-chain kernel stages dy with 16-byte vectors (8 bf16 channels): a bf16 C = 4 (mod 8)
-    // would read four channels past C (past the tensor on the last pixel), at 8-byte alignment
-    const int tvec = dtype == DT_BF16 ? 8 : 4;
-    // (x and g move as 4-channel vectors: the common check above is all their pitches need)
-    SEG_REQUIRE(C % tvec == 0 && lddy % tvec == 0,
-                "dwconv3x3_bwd_fused: C/lddy must be multiples of %d", tvec);
-    return launch_dw_row_bwd(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, dil, pro_mode, pro_scale,
-                             pro_shift, g, ldg, partial_w, partial_bn, grid_y, (hipStream_t)stream);
-  }
-  DwBwdArgs a;
-  a.dy = dy; a.x = x; a.g = g; a.w = w9c; a.pro_scale = pro_scale; a.pro_shift = pro_shift;
-  a.partial_w = partial_w; a.partial_bn = partial_bn;
-  a.lddy = lddy; a.ldx = ldx; a.ldg = ldg; a.N = N; a.H = H; a.W = W; a.C = C; a.dil = dil;
-  a.pro_mode = pro_mode; a.CV = C / vec; a.cvb_log2 = pick_cvb_log2(a.CV);
-  a.strips = (long)N * H * ((W + DW_TW - 1) / DW_TW);
-  SEG_REQUIRE(a.strips < (1L << 31), "dwconv3x3_bwd_fused: too many strips");
-  SEG_REQUIRE((long)N * H * W * lddy < (1L << 31), "dwconv3x3_bwd_fused: 32-bit offsets");
-  const int gx = (a.CV + (1 << a.cvb_log2) - 1) >> a.cvb_log2;
-  const dim3 grid(gx, grid_y);
-  const size_t lds = (size_t)DW_THREADS * 3 * vec * sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((dwconv_bwd_fused_kernel<bf16_t>), grid, dim3(DW_THREADS), lds, st, a);
-  else
-    hipLaunchKernelGGL((dwconv_bwd_fused_kernel<float>), grid, dim3(DW_THREADS), lds, st, a);
-  return check_launch("dwconv3x3_bwd_fused");
+  return seg::dw_bwd_fused("dwconv3x3_bwd_fused", dtype, dy, lddy, x, ldx, N, H, W, C, w9c, w_layout,
+                           dil, pro_mode, pro_scale, pro_shift, nullptr, 0, g, ldg, partial_w,
+                           partial_bn, grid_y, (hipStream_t)stream);
 }
 
 // dW [C][9] (= torch [C,1,3,3]) from the weight-gradient partials [R][9][C]

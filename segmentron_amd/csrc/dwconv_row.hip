@@ -18,7 +18,7 @@
 //   backward: tile = dy (raw); g[h][w] = mask * sum dy[h-(kh-1)d][w-(kw-1)d] w[kh][kw];
 //             accw[kh][kw] += dy_tap * act(x[h][w]); sums (g, g * x_raw)
 #include "common.h"
-#include "dwconv_tiled.h"
+#include "dwconv.h"
 
 namespace seg {
 
@@ -248,8 +248,6 @@ __global__ __launch_bounds__(RW_THREADS, BWD ? 2 : 3) void dwconv_row_kernel(con
 }
 
 // ---------------------------------------------------------------------------------------------
-bool dw_row_supported(int stride, int dil) { return stride == 1 && dil > 2 && dil <= 64; }
-
 constexpr size_t RW_LDS_MAX = 120 * 1024;
 
 // segment width: <= 160 pixels, equal segments, and a 3-row ring that fits RW_LDS_MAX

@@ -234,8 +234,10 @@ static int s2_grid_y(int C, int N, int H, int W) {
 
 }  // namespace seg
 
-// rows of the partial buffers seg_dwconv3x3_s2_bwd_fused writes (x is [N, H, W, C])
+// rows of the partial buffers seg_dwconv3x3_s2_bwd_fused writes (x is [N, H, W, C]); -1 where
+// there is no such launch (non-positive sizes, C not made of 4-channel vectors)
 extern "C" int seg_dwconv3x3_s2_grid_y(int C, int N, int H, int W) {
+  if (N < 1 || H < 1 || W < 1 || C < 4 || C % 4 != 0) return -1;
   return seg::s2_grid_y(C, N, H, W);
 }
 

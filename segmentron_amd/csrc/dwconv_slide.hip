@@ -27,7 +27,7 @@
 // inside an XCD's contiguous range (xcd_remap).  One partial row per (image, strip, column block).
 #include <type_traits>
 #include "common.h"
-#include "dwconv_slide.h"
+#include "dwconv.h"
 
 namespace seg {
 
@@ -600,8 +600,6 @@ __global__ __launch_bounds__(SL_THREADS, 2) void dwconv_slide_bwd_kernel(const D
 }
 
 // ---------------------------------------------------------------------------------------- host
-bool dw_slide_supported(int stride, int dil, int C) { return stride == 1 && dil == 1 && C % 4 == 0; }
-
 // Strips of ~43 rows: a strip pays a fixed price (tap / parameter loads, the first D rows' round
 // trip, two halo rows, the block reduction) that 13-row strips did not amortise on the 65 x 129
 // middle-flow map, while one strip per image leaves too few waves (profiles/r06_dw_slide.md:

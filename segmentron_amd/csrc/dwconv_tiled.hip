@@ -16,7 +16,7 @@
 // staged in LDS once, BatchNorm statistics / weight-gradient taps accumulate in registers across
 // tiles and are reduced once per block (deterministic, no atomics).
 #include "common.h"
-#include "dwconv_tiled.h"
+#include "dwconv.h"
 
 namespace seg {
 
@@ -1085,8 +1085,6 @@ int launch_dw_wgrad_finalize(const float* partial, int R, int C, float* out, hip
 }
 
 // ------------------------------------------------------------------ host side
-bool dw_tiled_supported(int stride, int dil) { return stride == 1 && (dil == 1 || dil == 2); }
-
 // rem: the r05 tiling with remainder tiles (forward / fused backward); the weight-gradient kernel
 // keeps the classic one
 // rem_pct: minimum share (percent) of the classic tile count the remainder tiles must save
@@ -1273,7 +1271,7 @@ int launch_dw_bwd_tiled(int dtype, const void* dy, long lddy, const void* x, lon
       hipLaunchKernelGGL((dwconv_bwd_tiled_kernel<TT, DD, RR, false>), grid, dim3(LT_THREADS),   \
                          tiled_lds<DD>(dtype, true), st, a);                                     \
   } while (0)
-  if (res != nullptr) {  // (dilation 1 only: dw_bwd_tiled_res_supported)
+  if (res != nullptr) {  // (dilation 1 only)
     if (dtype == DT_BF16) SEG_LT(bf16_t, 1, true); else SEG_LT(float, 1, true);
   } else if (dtype == DT_BF16) { if (dil == 1) SEG_LT(bf16_t, 1, false); else SEG_LT(bf16_t, 2, false); }
   else { if (dil == 1) SEG_LT(float, 1, false); else SEG_LT(float, 2, false); }

@@ -209,6 +209,27 @@ def _sync_bwd_finalize(partial, bn):
     return K.bn_bwd_finalize(sums, bn.count, bn.mean, bn.invstd, bn.gamma, scale)
 
 
+def _bn_bwd_finish(pb, bn, pw=None):
+    """BatchNorm-backward partials pb [R, 2C] -> (dgamma, dbeta, c0, c1, dW).  pw: the raw
+    weight-gradient partials [Rw, 9C] of a fused depthwise backward, reduced to dW [C,1,3,3] on the
+    way — by the same launch (K.dw_bwd_finalize*) where that kernel takes the rows; dW is None
+    without them.  (With pw, a SyncBatchNorm has its peer mailbox: _DwFn.backward asks for pw
+    only then.)"""
+    dW = None
+    if pw is not None and pb.shape[0] <= 1024:
+        if bn.group is None:
+            return K.dw_bwd_finalize(pb, pw, bn.count, bn.mean, bn.invstd, bn.gamma)
+        return K.dw_bwd_finalize_sync(parallel.mailbox(bn.group), pb, pw, bn.count, bn.mean,
+                                      bn.invstd, bn.gamma, parallel.grad_scale(bn.group))
+    if pw is not None:
+        dW = K.dw_wgrad_finalize(pw, bn.mean.numel())
+    if bn.group is None:
+        out = K.bn_bwd_finalize_p(pb, bn.count, bn.mean, bn.invstd, bn.gamma)
+    else:
+        out = _sync_bwd_finalize(pb, bn)
+    return (*out, dW)
+
+
 def bn_input_backward(g, x, bn, relu, chan_mul=None, inplace=False, elem_mul=None):
     """g = dLoss/d(act(x)*chan_mul*elem_mul)  ->  (dLoss/dx_raw, dgamma, dbeta)."""
     mode = (PRO_AFFINE if bn is not None else PRO_NONE) | int(relu)
@@ -227,11 +248,7 @@ def bn_input_backward(g, x, bn, relu, chan_mul=None, inplace=False, elem_mul=Non
         return K.bn_bwd_small(g, x, pro, bn.count, bn.mean, bn.invstd, bn.gamma, chan_mul,
                               elem_mul, bn.training, out=g if inplace else None)
     partial = K.bn_bwd_reduce_partial(g, x, pro, chan_mul, elem_mul)
-    if bn.group is None:
-        dgamma, dbeta, c0, c1 = K.bn_bwd_finalize_p(partial, bn.count, bn.mean, bn.invstd,
-                                                    bn.gamma)
-    else:
-        dgamma, dbeta, c0, c1 = _sync_bwd_finalize(partial, bn)
+    dgamma, dbeta, c0, c1, _ = _bn_bwd_finish(partial, bn)
     if not bn.training:
         c0 = c1 = None
     dx = K.bn_bwd_apply(g, x, pro, c0, c1, chan_mul, out=g if inplace else None,
@@ -473,6 +490,15 @@ def pack_dw_weight(w, flipped=False):
     return out
 
 
+def _dw_taps(weight, stride, dil, reversed=False):
+    """The taps in the form this layer's kernels read: the parameter itself where K.dw_tiled
+    (they reverse it in place for the data gradient), else its cached tap-major packing."""
+    if K.dw_tiled(stride, dil):
+        return weight.detach()
+    return cached_pack(weight, "dw_flip" if reversed else "dw",
+                       lambda: pack_dw_weight(weight, reversed))
+
+
 def _round_up(v, m):
     return (v + m - 1) // m * m
 
@@ -660,12 +686,8 @@ class _DwFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, in_gamma, in_beta, weight, spec):
-        if K.dw_tiled(spec.stride, spec.dil):
-            w = weight.detach()  # the tiled kernels read torch's [C,1,3,3] directly
-        else:
-            w = cached_pack(weight, "dw", lambda: pack_dw_weight(weight))
-        y, spec.partial = K.dwconv(x, w, spec.stride, spec.dil, spec.pro, spec.out,
-                                   spec.want_stats)
+        y, spec.partial = K.dwconv(x, _dw_taps(weight, spec.stride, spec.dil), spec.stride,
+                                   spec.dil, spec.pro, spec.out, spec.want_stats)
         spec.out = None  # (it IS y: kept, ctx -> spec -> y -> grad_fn -> ctx would be a cycle)
         ctx.spec = spec
         ctx.save_for_backward(x, weight)
@@ -679,78 +701,51 @@ class _DwFn(torch.autograd.Function):
         if K.nhwc(dy)[4] % K.vec_of(dy.dtype) != 0:
             dy = dy.contiguous()
         dx = dgamma = dbeta = None
-        tiled = K.dw_tiled(s.stride, s.dil)
-        big = x.numel() * x.element_size() >= (40 << 20)
-        strided = s.stride == 2 and s.dil == 1 and C % 4 == 0 and weight.dtype == torch.float32
-        if ctx.needs_input_grad[0] and ((s.stride == 1 and (tiled or big or s.dil > 2)) or strided):
-            # one pass over (dy, x): masked data gradient + weight-gradient partials + BN sums
-            # (LDS-tiled for dil <= 2; the strip version only pays on large tensors; stride 2 on
-            # its own kernel, csrc/dwconv_s2.hip)
-            bn = s.bn_in
-            # single-process BatchNorm on the input: the weight-gradient partials and the
-            # BatchNorm-backward partials are reduced by ONE launch (K.dw_bwd_finalize)
-            box = parallel.mailbox(bn.group) if (bn is not None and bn.group is not None) else None
-            both = bn is not None and (strided or tiled) and \
-                (bn.group is None or (box is not None and isinstance(bn.count, torch.Tensor)))
-            if strided:
+        bn = s.bn_in
+        tiled = K.dw_tiled(s.stride, s.dil)  # these kernels produce dW in torch's layout, too
+        # One pass over (dy, x): masked data gradient + weight-gradient partials + BN sums — every
+        # stride-1 layer, and stride 2 / dilation 1 on its own kernel (csrc/dwconv_s2.hip).
+        # Otherwise: weight gradient and data gradient separately.
+        fused_s2 = s.stride == 2 and s.dil == 1 and C % 4 == 0 and weight.dtype == torch.float32
+        if ctx.needs_input_grad[0] and (s.stride == 1 or fused_s2):
+            # raw: leave the weight-gradient partials to the launch that reduces the
+            # BatchNorm-backward ones (single-process BatchNorm, or SyncBatchNorm on the mailbox)
+            raw = bn is not None and (fused_s2 or tiled) and \
+                (bn.group is None or (parallel.mailbox(bn.group) is not None
+                                      and isinstance(bn.count, torch.Tensor)))
+            if fused_s2:
                 g, dW, pb = K.dwconv_bwd_fused_s2(x, dy, weight.detach().contiguous(), s.pro,
-                                                  want_bn=bn is not None, raw_dw=both)
-            elif tiled:
+                                                  want_bn=bn is not None, raw_dw=raw)
+            else:
                 res = None
                 if bn is None and s.fork is not None and s.fork.g is not None \
-                        and K.dwconv_bwd_fused_add_ok(x, s.dil):
+                        and K.dwconv_bwd_fused_add_ok(s.dil):
                     res = s.fork.take()  # the identity path's gradient rides in the store
                     if res.dtype != x.dtype or tuple(res.shape) != tuple(x.shape):
                         s.fork.g, res = res, None
-                g, dW, pb = K.dwconv_bwd_fused(x, dy, weight.detach(), s.dil, s.pro,
-                                               want_bn=bn is not None, torch_layout=True,
-                                               raw_dw=both, res=res)
-            else:
-                w9c = cached_pack(weight, "dw", lambda: pack_dw_weight(weight))
-                g, dW9c, pb = K.dwconv_bwd_fused(x, dy, w9c, s.dil, s.pro, want_bn=bn is not None)
-                dW = dW9c.t().reshape(C, 1, 3, 3).contiguous()
+                g, dW, pb = K.dwconv_bwd_fused(x, dy, _dw_taps(weight, 1, s.dil), s.dil, s.pro,
+                                               want_bn=bn is not None, torch_layout=tiled,
+                                               raw_dw=raw, res=res)
+                if not tiled:
+                    dW = K.dw_torch_layout(dW)
             if bn is None:
                 dx = g  # plain / ReLU input: the masked gradient is final
             else:
-                if both and pb.shape[0] <= 1024 and bn.group is None:
-                    dgamma, dbeta, c0, c1, dW = K.dw_bwd_finalize(pb, dW, bn.count, bn.mean,
-                                                                  bn.invstd, bn.gamma)
-                elif both and pb.shape[0] <= 1024:  # SyncBN: the exchange inside the same launch
-                    dgamma, dbeta, c0, c1, dW = K.dw_bwd_finalize_sync(
-                        box, pb, dW, bn.count, bn.mean, bn.invstd, bn.gamma,
-                        parallel.grad_scale(bn.group))
-                elif both:
-                    dW = K.dw_wgrad_finalize(dW, C)
-                    if bn.group is None:
-                        dgamma, dbeta, c0, c1 = K.bn_bwd_finalize_p(pb, bn.count, bn.mean,
-                                                                    bn.invstd, bn.gamma)
-                    else:
-                        dgamma, dbeta, c0, c1 = _sync_bwd_finalize(pb, bn)
-                elif bn.group is None:
-                    dgamma, dbeta, c0, c1 = K.bn_bwd_finalize_p(pb, bn.count, bn.mean, bn.invstd,
-                                                                bn.gamma)
-                else:
-                    dgamma, dbeta, c0, c1 = _sync_bwd_finalize(pb, bn)
+                dgamma, dbeta, c0, c1, dWsum = _bn_bwd_finish(pb, bn, dW if raw else None)
+                if raw:
+                    dW = dWsum
                 if not bn.training:
                     c0 = c1 = None
                 # the ReLU mask is already in g: apply only the affine part of the BN backward
                 dx = K.bn_bwd_apply(g, x, (PRO_AFFINE, bn.scale, bn.shift), c0, c1, out=g)
         else:
-            tiled = K.dw_tiled(s.stride, s.dil)
-            if tiled:
-                dW = K.dwconv_wgrad(x, dy, s.stride, s.dil, s.pro, torch_layout=True)
-            else:
-                dW9c = K.dwconv_wgrad(x, dy, s.stride, s.dil, s.pro)
-                dW = dW9c.t().reshape(C, 1, 3, 3).contiguous()
-            if ctx.needs_input_grad[0]:
-                if tiled:
-                    w = weight.detach()  # reversed inside the kernel
-                elif s.stride == 1:  # forward kernel with reversed taps
-                    w = cached_pack(weight, "dw_flip", lambda: pack_dw_weight(weight, True))
-                else:
-                    w = cached_pack(weight, "dw", lambda: pack_dw_weight(weight))
+            dW = K.dwconv_wgrad(x, dy, s.stride, s.dil, s.pro, torch_layout=tiled)
+            if not tiled:
+                dW = K.dw_torch_layout(dW)
+            if ctx.needs_input_grad[0]:  # (stride 1: the forward kernel on reversed taps)
+                w = _dw_taps(weight, s.stride, s.dil, reversed=s.stride == 1)
                 g = K.dwconv_dgrad(dy, w, s.stride, s.dil, (x.shape[1], x.shape[2]))
-                dx, dgamma, dbeta = bn_input_backward(g, x, s.bn_in, s.relu, inplace=True)
+                dx, dgamma, dbeta = bn_input_backward(g, x, bn, s.relu, inplace=True)
         if s.fork is not None and s.fork.g is not None and dx is not None:
             dx = dx + s.fork.take()  # (a path whose kernel cannot add it in its store)
         return dx, dgamma, dbeta, dW, None

@@ -220,14 +220,35 @@ def dw_tiled(stride, dil):
     return stride == 1 and dil in (1, 2)
 
 
-def _dw_weight_arg(w, C, stride, dil, flip):
-    """-> (tensor, w_layout).  [C,1,3,3]/[C,9] parameter tensors go straight to the tiled
-    kernels; the strip kernels take the tap-major [9, C] packing."""
+def _dw_weight_arg(w, C, stride, dil, reverse=False, is_reversed=False):
+    """-> (tensor, w_layout) for a launch that wants the taps in forward order, or (`reverse`: the
+    stride-1 data gradient) reversed.  w: the [C,1,3,3] / [C,9] parameter itself (bit 0; only
+    where dw_tiled), or a tap-major [9, C] packing, `is_reversed` already or not.  Where dw_tiled
+    the kernels reverse while they stage the taps (bit 1); the others get a reversed copy."""
+    tiled = dw_tiled(stride, dil)
     if w.dim() == 4 or (w.dim() == 2 and w.shape == (C, 9) and C != 9):
-        if not dw_tiled(stride, dil):
-            raise ValueError("depthwise strip kernels need tap-major [9, C] weights")
-        return w, 1 | (2 if flip else 0)
-    return w, (2 if flip else 0) if dw_tiled(stride, dil) else 0
+        if not tiled:
+            raise ValueError("depthwise row-chain / strip kernels need tap-major [9, C] weights")
+        return w, 1 | (2 if reverse else 0)
+    reverse = reverse and not is_reversed
+    if reverse and not tiled:
+        return w.flip(0).contiguous(), 0
+    return w, 2 if reverse else 0
+
+
+def _dw_grid_y(query, *args):
+    """Partial rows of a depthwise launch; raises before anything is allocated where the library
+    has no such launch (-1: an empty tensor, C not made of the kernels' channel vectors)."""
+    gy = LIB.query(query, *args)
+    if gy < 1:
+        raise ValueError("%s%s: no such depthwise launch (empty tensor, or C is not a multiple "
+                         "of the kernels' channel vector)" % (query, args))
+    return gy
+
+
+def dw_torch_layout(dW9c):
+    """weight gradient [9, C] (tap-major) -> the parameter's [C,1,3,3]."""
+    return dW9c.t().reshape(-1, 1, 3, 3).contiguous()
 
 
 def dwconv(x, w9c, stride, dil, pro=None, out=None, want_stats=False):
@@ -238,8 +259,8 @@ def dwconv(x, w9c, stride, dil, pro=None, out=None, want_stats=False):
     if out is None:
         out = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
     ldy = nhwc(out)[4]
-    w, layout = _dw_weight_arg(w9c, C, stride, dil, False)
-    gy = LIB.query("seg_dwconv_grid_y", _DT[x.dtype], C, N, Ho, Wo, stride, dil, 0)
+    w, layout = _dw_weight_arg(w9c, C, stride, dil)
+    gy = _dw_grid_y("seg_dwconv_grid_y", _DT[x.dtype], C, N, Ho, Wo, stride, dil, 0)
     partial = torch.empty((gy, 2, C), dtype=torch.float32, device=x.device) if want_stats else None
     LIB.call("seg_dwconv3x3", _DT[x.dtype], 0, _p(x), ldx, N, Hi, Wi, C, _p(w), layout, stride,
              dil, mode, _p(ps), _p(pt), _p(out), ldy, Ho, Wo, _p(partial), gy, _stream())
@@ -265,19 +286,11 @@ def dwconv_dgrad(dy, w9c, stride, dil, in_hw, flipped=True, out=None):
     N, Ho, Wo, C, lddy = nhwc(dy)
     Hi, Wi = in_hw
     dx, lddx = _dw_grad_out(out, N, Hi, Wi, C, dy)
-    gy = LIB.query("seg_dwconv_grid_y", _DT[dy.dtype], C, N, Hi, Wi, stride, dil, 0)
-    if stride == 1:
-        if w9c.dim() == 4:
-            w, layout = w9c, 3
-        elif dw_tiled(stride, dil):
-            w, layout = w9c, 0 if flipped else 2
-        else:
-            w, layout = (w9c if flipped else w9c.flip(0).contiguous()), 0
-        LIB.call("seg_dwconv3x3", _DT[dy.dtype], 0, _p(dy), lddy, N, Ho, Wo, C, _p(w), layout, 1,
-                 dil, PRO_NONE, 0, 0, _p(dx), lddx, Hi, Wi, 0, gy, _stream())
-    else:
-        LIB.call("seg_dwconv3x3", _DT[dy.dtype], 1, _p(dy), lddy, N, Ho, Wo, C, _p(w9c), 0, stride,
-                 dil, PRO_NONE, 0, 0, _p(dx), lddx, Hi, Wi, 0, gy, _stream())
+    gy = _dw_grid_y("seg_dwconv_grid_y", _DT[dy.dtype], C, N, Hi, Wi, stride, dil, 0)
+    # stride 1: the forward launch (mode 0) on reversed taps; strided: the data-gradient one
+    w, layout = _dw_weight_arg(w9c, C, stride, dil, stride == 1, flipped)
+    LIB.call("seg_dwconv3x3", _DT[dy.dtype], int(stride != 1), _p(dy), lddy, N, Ho, Wo, C, _p(w),
+             layout, stride, dil, PRO_NONE, 0, 0, _p(dx), lddx, Hi, Wi, 0, gy, _stream())
     return dx
 
 
@@ -313,7 +326,7 @@ def dw_bwd_finalize_sync(box, pb, pw, count_dev, mean, invstd, gamma, grad_scale
     return out[0], out[1], out[2], out[3], dW
 
 
-def dwconv_bwd_fused_add_ok(x, dil):
+def dwconv_bwd_fused_add_ok(dil):
     """Can the fused depthwise backward add a second gradient in its store path?"""
     return bool(LIB.query("seg_dwconv3x3_bwd_fused_add_ok", int(dil)))
 
@@ -328,11 +341,8 @@ def dwconv_bwd_fused(x, dy, w, dil, pro=None, want_bn=False, torch_layout=False,
     lddy = nhwc(dy)[4]
     mode, ps, pt = _pro(pro)
     g, ldg = _dw_grad_out(out, N, H, W, C, x)
-    tiled = dw_tiled(1, dil)
-    layout = 1 if w.dim() == 4 else 0
-    if layout and not tiled:
-        raise ValueError("depthwise strip kernels need tap-major [9, C] weights")
-    gy = LIB.query("seg_dwconv_grid_y", _DT[x.dtype], C, N, H, W, 1, dil, 1)
+    w, layout = _dw_weight_arg(w, C, 1, dil)
+    gy = _dw_grid_y("seg_dwconv_grid_y", _DT[x.dtype], C, N, H, W, 1, dil, 1)
     pw = torch.empty((gy, 9 * C), dtype=torch.float32, device=x.device)
     pb = torch.empty((gy, 2 * C), dtype=torch.float32, device=x.device) if want_bn else None
     if res is not None:  # g = masked dgrad + res (the other gradient of a forked activation)
@@ -346,9 +356,7 @@ def dwconv_bwd_fused(x, dy, w, dil, pro=None, want_bn=False, torch_layout=False,
     if raw_dw:  # the caller reduces pw together with pb (dw_bwd_finalize)
         return g, pw, pb
     if torch_layout:
-        dW = torch.empty((C, 1, 3, 3), dtype=torch.float32, device=x.device)
-        LIB.call("seg_dwconv3x3_wgrad_finalize", _p(pw), gy, C, _p(dW), _stream())
-        return g, dW, pb
+        return g, dw_wgrad_finalize(pw, C), pb
     return g, colsum(pw, f64=False).view(9, C), pb
 
 
@@ -361,16 +369,12 @@ def dwconv_bwd_fused_s2(x, dy, w, pro=None, want_bn=False, raw_dw=False, out=Non
     assert (Nd, Ho, Wo, Cd) == (N, (H + 1) // 2, (W + 1) // 2, C) and tuple(w.shape) == (C, 1, 3, 3)
     mode, ps, pt = _pro(pro)
     g, ldg = _dw_grad_out(out, N, H, W, C, x)
-    gy = LIB.query("seg_dwconv3x3_s2_grid_y", C, N, H, W)
+    gy = _dw_grid_y("seg_dwconv3x3_s2_grid_y", C, N, H, W)
     pw = torch.empty((gy, 9 * C), dtype=torch.float32, device=x.device)
     pb = torch.empty((gy, 2 * C), dtype=torch.float32, device=x.device) if want_bn else None
     LIB.call("seg_dwconv3x3_s2_bwd_fused", _DT[x.dtype], _p(dy), lddy, _p(x), ldx, N, H, W, C,
              _p(w), mode, _p(ps), _p(pt), _p(g), ldg, _p(pw), _p(pb), gy, _stream())
-    if raw_dw:
-        return g, pw, pb
-    dW = torch.empty((C, 1, 3, 3), dtype=torch.float32, device=x.device)
-    LIB.call("seg_dwconv3x3_wgrad_finalize", _p(pw), gy, C, _p(dW), _stream())
-    return g, dW, pb
+    return g, (pw if raw_dw else dw_wgrad_finalize(pw, C)), pb
 
 
 def dwconv_wgrad(x, dy, stride, dil, pro=None, torch_layout=False):
@@ -378,14 +382,12 @@ def dwconv_wgrad(x, dy, stride, dil, pro=None, torch_layout=False):
     N, Hi, Wi, C, ldx = nhwc(x)
     _, Ho, Wo, _, lddy = nhwc(dy)
     mode, ps, pt = _pro(pro)
-    gy = LIB.query("seg_dwconv_grid_y", _DT[x.dtype], C, N, Ho, Wo, stride, dil, 2)
+    gy = _dw_grid_y("seg_dwconv_grid_y", _DT[x.dtype], C, N, Ho, Wo, stride, dil, 2)
     partial = torch.empty((gy, 9 * C), dtype=torch.float32, device=x.device)
     LIB.call("seg_dwconv3x3_wgrad", _DT[x.dtype], _p(x), ldx, N, Hi, Wi, C, _p(dy), lddy, Ho, Wo,
              stride, dil, mode, _p(ps), _p(pt), _p(partial), gy, _stream())
     if torch_layout:
-        out = torch.empty((C, 1, 3, 3), dtype=torch.float32, device=x.device)
-        LIB.call("seg_dwconv3x3_wgrad_finalize", _p(partial), gy, C, _p(out), _stream())
-        return out
+        return dw_wgrad_finalize(partial, C)
     return colsum(partial, f64=False).view(9, C)
 
 

@@ -137,8 +137,8 @@ def depthwise_conv3x3(x: torch.Tensor, weight: torch.Tensor, stride: int, dilati
     """nn.Conv2d(C, C, 3, stride, padding=dilation, dilation, groups=C) on NHWC x, weight
     [C,1,3,3] fp32 (segmentron/modules/basic.py:38-40)."""
     from . import functional as F
-    w = weight if K.dw_tiled(stride, dilation) else F.pack_dw_weight(weight)
-    y, _ = K.dwconv(x, w, stride, dilation, _PRO_RELU if relu_in else None)
+    y, _ = K.dwconv(x, F._dw_taps(weight, stride, dilation), stride, dilation,
+                    _PRO_RELU if relu_in else None)
     return y
 
 
@@ -154,21 +154,16 @@ def depthwise_conv3x3_backward(x: torch.Tensor, dy: torch.Tensor, weight: torch.
                                stride: int, dilation: int, relu_in: bool
                                ) -> Tuple[torch.Tensor, torch.Tensor]:
     from . import functional as F
-    C = weight.shape[0]
     pro = _PRO_RELU if relu_in else None
     if K.nhwc(dy)[4] % K.vec_of(dy.dtype) != 0:
         dy = dy.contiguous()
     tiled = K.dw_tiled(stride, dilation)
-    if stride == 1 and tiled:  # one pass: masked data gradient + weight gradient
+    if tiled:  # one pass: masked data gradient + weight gradient
         g, dW, _ = K.dwconv_bwd_fused(x, dy, weight, dilation, pro, want_bn=False,
                                       torch_layout=True)
         return g, dW
-    if tiled:
-        dW = K.dwconv_wgrad(x, dy, stride, dilation, pro, torch_layout=True)
-        w = weight
-    else:
-        dW = K.dwconv_wgrad(x, dy, stride, dilation, pro).t().reshape(C, 1, 3, 3).contiguous()
-        w = F.pack_dw_weight(weight, flipped=stride == 1)
+    dW = K.dw_torch_layout(K.dwconv_wgrad(x, dy, stride, dilation, pro))
+    w = F._dw_taps(weight, stride, dilation, reversed=stride == 1)
     g = K.dwconv_dgrad(dy, w, stride, dilation, (x.shape[1], x.shape[2]))
     if relu_in:
         g = K.bn_bwd_apply(g, x, _PRO_RELU, out=g)

@@ -313,6 +313,54 @@ def test_kernel_selection_queries_of_the_c_library():
     assert q("seg_bn_bwd_grid_y", F32, 728, 16770) == 256 and q("seg_bn_bwd_grid_y", F32, 2052, 100000) == 31
 
 
+def test_depthwise_grid_queries_equal_the_recorded_ones_and_refuse_bad_input(golden_dir):
+    """tests/golden/dw_grid_queries.npz (oracle/gen_golden_dw_grid.py) holds what the depthwise
+    grid queries answered BEFORE the routing moved into dw_route (csrc/dwconv.hip), recorded from
+    that commit's build: every family, both dtypes, map sizes on both sides of the 1024-row limit
+    of the one-launch finalize.  The library answers the same at every point — and -1, not a
+    division by zero, where there is no such launch."""
+    import numpy as np
+    from segmentron_amd import _lib
+    q = _lib.LIB.query
+    BF16, F32 = 1, 0
+    z = np.load(os.path.join(golden_dir, "dw_grid_queries.npz"))
+    want = z["grid_y"]
+    Cs, shapes = z["C"].tolist(), z["shapes"].tolist()
+    strides, dils, kinds = z["strides"].tolist(), z["dils"].tolist(), z["kinds"].tolist()
+    got = np.full_like(want, -2)
+    for dt in (F32, BF16):
+        for ci, C in enumerate(Cs):
+            if C % (8 if dt == BF16 else 4):
+                continue
+            for si, (N, H, W) in enumerate(shapes):
+                for ti, stride in enumerate(strides):
+                    for di, dil in enumerate(dils):
+                        for kind in kinds:
+                            got[dt, ci, si, ti, di, kind] = q("seg_dwconv_grid_y", dt, C, N, H, W,
+                                                              stride, dil, kind)
+    assert (want != -2).sum() == 53856 and want.max() == 2048 and want[want != -2].min() == 1
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, "%d points differ, first (dtype, C, shape, stride, dil, kind index) %s: " \
+        "%d, recorded %d" % (len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
+    s2 = [[q("seg_dwconv3x3_s2_grid_y", C, N, H, W) for (N, H, W) in shapes] for C in Cs]
+    assert s2 == z["s2_grid_y"].tolist()
+    assert [q("seg_dwconv3x3_bwd_fused_add_ok", d) for d in (1, 2, 3)] == z["add_ok"].tolist()
+    # no such launch: fewer channels than one vector of the family's geometry, C off the vector
+    # width, empty tensors (these divided by zero before)
+    assert q("seg_dwconv_grid_y", BF16, 4, 1, 1, 1, 1, 1, 2) == -1
+    for kind in kinds:
+        for stride, dil in ((1, 1), (1, 2), (2, 1), (1, 6), (1, 100), (3, 3)):
+            assert q("seg_dwconv_grid_y", F32, 6, 1, 9, 20, stride, dil, kind) == -1
+            for dt in (F32, BF16):
+                assert q("seg_dwconv_grid_y", dt, 0, 1, 9, 20, stride, dil, kind) == -1
+                assert q("seg_dwconv_grid_y", dt, 16, 1, 0, 20, stride, dil, kind) == -1
+                assert q("seg_dwconv_grid_y", dt, 16, 0, 9, 20, stride, dil, kind) == -1
+                assert q("seg_dwconv_grid_y", dt, 16, 1, 9, 0, stride, dil, kind) == -1
+    for args in ((0, 1, 9, 20), (6, 1, 9, 20), (2, 1, 9, 20), (16, 1, 0, 20), (16, 0, 9, 20),
+                 (16, 1, 9, 0)):
+        assert q("seg_dwconv3x3_s2_grid_y", *args) == -1
+
+
 def test_frozen_batchnorm_module_contract():
     """get_norm('FrozenBN') — segmentron/modules/batch_norm.py:10-104,107-132: four BUFFERS, the
     reference's state_dict keys, its version-3 loading rule, convert_frozen_batchnorm; 'GN'
