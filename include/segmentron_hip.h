@@ -319,6 +319,34 @@ int seg_adaptive_avgpool_partial(int dtype, const void* x, long ldx, int N, int 
 int seg_adaptive_avgpool_bwd(int dtype, void* gx, long ldgx, int N, int H, int W, int C, int o,
                              const void* gy, long ldgy, void* stream);
 
+/* ---- channel attention: squeeze (global average pool) + sigmoid gate (csrc/chan_gate.hip) -----
+ * Replaces nn.AdaptiveAvgPool2d(1) -> ... -> nn.Sigmoid() -> `x * attention` of
+ * segmentron/models/bisenet.py:106-120,170-186.  NHWC, HW = H*W pixels per image, `chunks` =
+ * seg_apply_pool_chunks(N, HW, C) pixel chunks per image; a / radd / v are fp32 [N][C].  Partial
+ * rows are fp32, written per (chunk, image) and summed over the chunks in index order: no atomics,
+ * bit-identical results on every launch.
+ *   seg_apply_pool_fwd   y = act(x) (y nullable: pool only) and partial[chunks][N][C] = sums of the
+ *                        fp32 activated values (seg_colsum over the chunks, divide by HW)
+ *   seg_chan_gate_fwd    y = x * (identity + sigmoid(a[n][c])) + r + radd[n][c]   (r, radd nullable)
+ *   seg_chan_gate_bwd    dx = dy * (identity + sigmoid(a)) (dx nullable) and
+ *                        partial[chunks][N][2][C] = (sum_hw dy*x, sum_hw dy)
+ *   seg_chan_gate_bwd_finalize   da = s(1-s) * sum dy*x, dradd = sum dy   (either nullable)
+ *   seg_bcast_add        y = g + v[n][c] * scale (g nullable: the broadcast alone; y may be g) */
+int seg_apply_pool_chunks(int N, long HW, int C);
+int seg_apply_pool_fwd(int dtype, const void* x, long ldx, int pro_mode, const float* pro_scale,
+                       const float* pro_shift, void* y, long ldy, int N, long HW, int C,
+                       float* partial, int chunks, void* stream);
+int seg_chan_gate_fwd(int dtype, const void* x, long ldx, const float* a_pre, int identity,
+                      const void* r, long ldr, const float* radd, void* y, long ldy, int N, long HW,
+                      int C, int chunks, void* stream);
+int seg_chan_gate_bwd(int dtype, const void* dy, long lddy, const void* x, long ldx,
+                      const float* a_pre, int identity, void* dx, long lddx, int N, long HW, int C,
+                      float* partial, int chunks, void* stream);
+int seg_chan_gate_bwd_finalize(const float* partial, int chunks, int N, int C, const float* a_pre,
+                               float* da, float* dradd, void* stream);
+int seg_bcast_add(int dtype, const void* g, long ldg, const float* v, float scale, void* y,
+                  long ldy, int N, long HW, int C, int chunks, void* stream);
+
 /* ---- F.interpolate(mode='bilinear') ---------------------------------------------------------
  * Replaces segmentron/models/deeplabv3_plus.py:39,44,71; segmentron/modules/module.py:64,96;
  * segmentron/models/segbase.py:83.  NHWC -> NHWC with optional prologue and per-(n,c) multiplier. */

@@ -917,6 +917,10 @@ class LogitsView:
     lo: torch.Tensor
     out_hw: tuple
     align_corners: bool = True
+    # largest resize factor (H-1)/(Hi-1) handed to the fused loss: 8.1 for every model whose
+    # heads sit at output stride 8; BiSeNet's first aux head (stride 16) asks for the kernels'
+    # third tier, 16.1
+    max_scale: float = 8.1
     _full: object = dataclasses.field(default=None, init=False, repr=False)
 
     def __post_init__(self):
@@ -971,7 +975,8 @@ class LogitsView:
                 and hi > 1 and wi > 1
                 # seg_upsample_ce_bwd's own criterion: 1/scale = (H-1)/(Hi-1) <= 8.1 (r05: the
                 # output-stride-8 heads of PSPNet / DANet / CCNet; 4.1 before)
-                and self.out_hw[0] - 1 <= 8.1 * (hi - 1) and self.out_hw[1] - 1 <= 8.1 * (wi - 1))
+                and self.out_hw[0] - 1 <= self.max_scale * (hi - 1)
+                and self.out_hw[1] - 1 <= self.max_scale * (wi - 1))
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
@@ -1013,6 +1018,89 @@ class _GapFn(torch.autograd.Function):
         H, W, dt = ctx.meta
         gs = (g.float() / float(H * W)).to(dt).contiguous()
         return K.bilinear(gs, (H, W), None, None, True), None
+
+
+class ApplyPoolSpec:
+    def __init__(self, a, want_y=True, own_grad=False):
+        self.bn, self.relu, self.pro = a.bn, a.relu, a.pro
+        # want_y False: pool only.  own_grad: the gradient that reaches y is a tensor nobody else
+        # holds (channel_gate: the fresh dx of _ChanGateFn), so the pool's gradient is added to it
+        # in place
+        self.want_y, self.own_grad = want_y, own_grad
+
+
+class _ApplyPoolFn(torch.autograd.Function):
+    """(y, pooled) = (act(x), nn.AdaptiveAvgPool2d(1)(act(x))) of a deferred activation in ONE pass
+    over x for all images (csrc/chan_gate.hip seg_apply_pool_fwd).  pooled is [N,1,1,C] float32
+    in every compute dtype (see global_avg_pool: the BatchNorm behind it sees N samples per
+    channel); y is x itself where nothing is pending.  Backward receives both gradients at once:
+    g = g_y + g_pooled / HW by one broadcast-add, then the usual BatchNorm(+ReLU) backward."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, spec):
+        N, H, W, C = x.shape
+        plain = spec.bn is None and not spec.relu
+        y, sums = K.apply_pool(x, spec.pro, want_y=spec.want_y and not plain)
+        ctx.spec = spec
+        ctx.save_for_backward(x)
+        pooled = (sums / float(H * W)).view(N, 1, 1, C)
+        if not spec.want_y:
+            return pooled
+        return (x.view(x.shape) if plain else y), pooled
+
+    @staticmethod
+    def backward(ctx, *grads):
+        (x,) = ctx.saved_tensors
+        s = ctx.spec
+        g_y, g_p = grads if s.want_y else (None, grads[0])
+        N, H, W, C = x.shape
+        if g_y is not None:
+            if g_y.dtype != x.dtype or not _sum_n_operand_ok(g_y, K.vec_of(x.dtype)):
+                g_y, own = g_y.to(x.dtype).contiguous(), True
+            else:
+                own = s.own_grad
+        if g_p is None:
+            if g_y is None:
+                return None, None, None, None
+            g, own = g_y, False
+        else:
+            v = g_p.reshape(N, C).float().contiguous()
+            # (a gradient somebody else may still read is not touched: the sum goes elsewhere)
+            g = K.bcast_add(g_y, v, 1.0 / float(H * W), like=x, inplace=g_y is not None and own)
+            own = True
+        dx, dgamma, dbeta = bn_input_backward(g, x, s.bn, s.relu, inplace=own)
+        return dx, dgamma, dbeta, None
+
+
+class _ChanGateFn(torch.autograd.Function):
+    """y = x * (identity + sigmoid(a)) + r + radd: the channel-attention gate of BiSeNet's
+    AttentionRefinmentModule (`x * s`, bisenet.py:116-120) and FeatureFusion (`x + x * s`,
+    bisenet.py:181-186) with the sums that follow it in ContextPath.forward (`feature +=
+    last_feature`, bisenet.py:159-161).  x, r plain NHWC; a, radd float32 [N,1,1,C]."""
+
+    @staticmethod
+    def forward(ctx, x, a, r, radd, identity):
+        N, H, W, C = x.shape
+        a2 = a.detach().reshape(N, C).contiguous()
+        radd2 = None if radd is None else radd.detach().reshape(N, C).contiguous()
+        ctx.identity = identity
+        ctx.save_for_backward(x, a2)
+        return K.chan_gate(x, a2, identity, r, radd2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, a2 = ctx.saved_tensors
+        N, H, W, C = x.shape
+        if dy.dtype != x.dtype or not _sum_n_operand_ok(dy, K.vec_of(x.dtype)):
+            dy = dy.to(x.dtype).contiguous()
+        need = ctx.needs_input_grad
+        dx, da, dradd = K.chan_gate_bwd(dy, x, a2, ctx.identity, want_dx=need[0], want_da=need[1],
+                                        want_dradd=need[3])
+        if da is not None:
+            da = da.view(N, 1, 1, C)
+        if dradd is not None:
+            dradd = dradd.view(N, 1, 1, C)
+        return dx, da, (dy if need[2] else None), dradd, None  # (d/dr is dy itself: no copy)
 
 
 class PoolSpec:
@@ -1442,11 +1530,12 @@ def want_lazy_logits(training):
     return _LAZY_EVAL[0] and not torch.is_grad_enabled()
 
 
-def logits_to_nchw(x, out_hw, align_corners=True, lazy=False):
+def logits_to_nchw(x, out_hw, align_corners=True, lazy=False, max_scale=8.1):
     """Model boundary.  lazy (training): a LogitsView, so that a following cross-entropy runs
-    fused on the low-resolution logits; otherwise the materialised [N, C, H, W] float32 tensor."""
+    fused on the low-resolution logits (up to a resize factor of max_scale: 8.1, or 16.1 for a
+    head at output stride 16); otherwise the materialised [N, C, H, W] float32 tensor."""
     if lazy and align_corners:
-        return LogitsView(x, out_hw, align_corners)
+        return LogitsView(x, out_hw, align_corners, max_scale)
     return _LogitsFn.apply(x, tuple(out_hw), align_corners)
 
 
@@ -1461,6 +1550,38 @@ def global_avg_pool(x, keep_fp32=False):
     squared gradient error, the exit-flow weights behind it most of the rest.  The branch is two
     rows of a GEMM: float32 costs nothing."""
     return _GapFn.apply(x, torch.float32 if keep_fp32 else x.dtype)
+
+
+def global_avg_pool_all(act, keep_fp32=True):
+    """nn.AdaptiveAvgPool2d(1) of a deferred activation -> [N,1,1,C], all images in one launch and
+    the pending BatchNorm / ReLU applied on the way (no materialised copy).  keep_fp32: as
+    global_avg_pool."""
+    g, b = act.params
+    pooled = _ApplyPoolFn.apply(act.t, g, b, ApplyPoolSpec(act, want_y=False))
+    return pooled if keep_fp32 else pooled.to(act.t.dtype)
+
+
+def channel_gate(act, branch, identity=False, residual=None, bcast_residual=None):
+    """Squeeze-and-gate channel attention -> plain NHWC tensor
+        x * (identity + sigmoid(branch(mean_hw(x)))) + residual + bcast_residual,   x = act(raw).
+    branch: callable, pooled Act [N,1,1,C] (float32 in every compute dtype) -> the pre-sigmoid Act
+    (a chain of 1x1 conv + BatchNorm + ReLU on F.conv_bn, which then runs in float32 like the
+    ASPP image-pooling branch).  residual: plain NHWC tensor of x's shape; bcast_residual: an Act
+    [N,1,1,C] (a 1x1 map resized with align_corners=True is constant per image and channel).
+    Passes over the activation: forward reads raw / writes x, reads x / writes the result;
+    backward one reduce-and-scale pass, one in-place broadcast add, then the BatchNorm backward
+    of the producer."""
+    g, b = act.params
+    y, pooled = _ApplyPoolFn.apply(act.t, g, b, ApplyPoolSpec(act, own_grad=True))
+    a = materialize(branch(Act(pooled)))
+    if a.dtype != torch.float32:
+        a = a.float()
+    radd = None
+    if bcast_residual is not None:
+        radd = materialize(bcast_residual)
+        if radd.dtype != torch.float32:
+            radd = radd.float()
+    return _ChanGateFn.apply(y, a, residual, radd, bool(identity))
 
 
 def max_pool(act, k, stride, pad):

@@ -324,7 +324,7 @@ class TransparentTrainGraph:
             self.segments[key] = seg
         seg.x.copy_(x)
         lo = _GraphedSegment.apply(seg.anchor, seg)
-        return seg.container(t if m is None else F.LogitsView(t, m[0], m[1])
+        return seg.container(t if m is None else F.LogitsView(t, *m)
                              for t, m in zip(lo, seg.meta))
 
     # -- capture of one shape
@@ -366,8 +366,8 @@ class TransparentTrainGraph:
                 raise RuntimeError("transparent capture needs tensor / LogitsView outputs")
             seg.container = list if isinstance(outs, list) else tuple
             seg.lo = [o.lo if isinstance(o, F.LogitsView) else o for o in outs]
-            seg.meta = [(o.out_hw, o.align_corners) if isinstance(o, F.LogitsView) else None
-                        for o in outs]
+            seg.meta = [(o.out_hw, o.align_corners, o.max_scale) if isinstance(o, F.LogitsView)
+                        else None for o in outs]
             seg.grad_lo = [torch.zeros_like(t) for t in seg.lo]
             with F.restrict_pack_plan(seg.params), capture(seg.bwd):
                 grads = torch.autograd.grad(seg.lo, leaves, seg.grad_lo, allow_unused=True)

@@ -742,6 +742,90 @@ def adaptive_avgpool_bwd(gy, in_hw):
     return gx
 
 
+# ---- channel attention: squeeze + sigmoid gate (csrc/chan_gate.hip) ----------------------------
+def _gate_chunks(N, HW, C):
+    chunks = LIB.query("seg_apply_pool_chunks", N, HW, C)
+    if chunks < 1:
+        raise ValueError("seg_apply_pool_chunks(%d, %d, %d): empty tensor" % (N, HW, C))
+    return chunks
+
+
+def _nc(t, N, C, what):
+    if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == N * C):
+        raise RuntimeError("%s: expected a contiguous float32 [%d, %d] tensor" % (what, N, C))
+    return t
+
+
+def apply_pool(x, pro=None, want_y=True, out=None):
+    """-> (y = act(x) in x.dtype | None, sums fp32 [N, C] of the fp32 activated values per image):
+    one pass, all images in one launch."""
+    N, H, W, C, ldx = nhwc(x)
+    mode, s, t = _pro(pro)
+    y, ldy = None, 0
+    if want_y:
+        y = out if out is not None else torch.empty((N, H, W, C), dtype=x.dtype, device=x.device)
+        assert tuple(y.shape) == (N, H, W, C) and y.dtype == x.dtype
+        ldy = nhwc(y)[4]
+    chunks = _gate_chunks(N, H * W, C)
+    partial = torch.empty((chunks, N * C), dtype=torch.float32, device=x.device)
+    LIB.call("seg_apply_pool_fwd", _DT[x.dtype], _p(x), ldx, mode, _p(s), _p(t), _p(y), ldy, N,
+             H * W, C, _p(partial), chunks, _stream())
+    sums = partial[0] if chunks == 1 else colsum(partial, f64=False)
+    return y, sums.view(N, C)
+
+
+def chan_gate(x, a, identity=False, r=None, radd=None, out=None):
+    """y = x * (identity + sigmoid(a[n][c])) + r + radd[n][c]; a / radd fp32 [N, C]."""
+    N, H, W, C, ldx = nhwc(x)
+    _nc(a, N, C, "chan_gate a")
+    _nc(radd, N, C, "chan_gate radd")
+    ldr = 0
+    if r is not None:
+        assert tuple(r.shape) == (N, H, W, C) and r.dtype == x.dtype
+        ldr = nhwc(r)[4]
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == (N, H, W, C) and out.dtype == x.dtype
+    LIB.call("seg_chan_gate_fwd", _DT[x.dtype], _p(x), ldx, _p(a), int(bool(identity)), _p(r), ldr,
+             _p(radd), _p(out), nhwc(out)[4], N, H * W, C, _gate_chunks(N, H * W, C), _stream())
+    return out
+
+
+def chan_gate_bwd(dy, x, a, identity=False, want_dx=True, want_da=True, want_dradd=True):
+    """-> (dx = dy * (identity + sigmoid(a)), da = s(1-s) * sum_hw dy*x, dradd = sum_hw dy)."""
+    N, H, W, C, lddy = nhwc(dy)
+    assert tuple(x.shape) == (N, H, W, C) and x.dtype == dy.dtype
+    _nc(a, N, C, "chan_gate_bwd a")
+    ldx = nhwc(x)[4]
+    dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device) if want_dx else None
+    chunks = _gate_chunks(N, H * W, C)
+    partial = torch.empty((chunks, N, 2, C), dtype=torch.float32, device=dy.device)
+    LIB.call("seg_chan_gate_bwd", _DT[dy.dtype], _p(dy), lddy, _p(x), ldx, _p(a),
+             int(bool(identity)), _p(dx), C, N, H * W, C, _p(partial), chunks, _stream())
+    da = torch.empty((N, C), dtype=torch.float32, device=dy.device) if want_da else None
+    dradd = torch.empty((N, C), dtype=torch.float32, device=dy.device) if want_dradd else None
+    if want_da or want_dradd:
+        LIB.call("seg_chan_gate_bwd_finalize", _p(partial), chunks, N, C, _p(a), _p(da), _p(dradd),
+                 _stream())
+    return dx, da, dradd
+
+
+def bcast_add(g, v, scale, like=None, inplace=True):
+    """g[n,h,w,c] += v[n][c] * scale (v fp32 [N, C]), in place or (`inplace` False) into a fresh
+    tensor; g None: a fresh tensor shaped and typed `like` that holds the broadcast alone."""
+    ref = g if g is not None else like
+    N, H, W, C, ldr = nhwc(ref)
+    _nc(v, N, C, "bcast_add v")
+    ldg = 0 if g is None else ldr
+    if g is None or not inplace:
+        out = torch.empty((N, H, W, C), dtype=ref.dtype, device=ref.device)
+    else:
+        out = g
+    LIB.call("seg_bcast_add", _DT[out.dtype], _p(g), ldg, _p(v), float(scale), _p(out),
+             nhwc(out)[4], N, H * W, C, _gate_chunks(N, H * W, C), _stream())
+    return out
+
+
 _BIN_AREAS = {}
 
 

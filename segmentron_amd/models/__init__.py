@@ -8,3 +8,4 @@ from .ccnet import CCNet  # noqa: F401
 from .fast_scnn import FastSCNN  # noqa: F401
 from .danet import DANet  # noqa: F401
 from .pointrend import PointRend  # noqa: F401
+from .bisenet import BiSeNet  # noqa: F401

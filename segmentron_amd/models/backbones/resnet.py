@@ -151,7 +151,9 @@ class ResNetV1(nn.Module):
 
     def forward(self, x):
         from ... import compute_dtype
-        a = F.Act(F.image_to_nhwc(x, compute_dtype()))
+        # (an Act: the caller's own F.image_to_nhwc of the image, shared with another path —
+        # BiSeNet's spatial path)
+        a = x if isinstance(x, F.Act) else F.Act(F.image_to_nhwc(x, compute_dtype()))
         if self.deep_stem:
             s = self.conv1
             a = F.conv_bn(a, s[0], s[1])

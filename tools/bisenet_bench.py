@@ -1,0 +1,199 @@
+"""BiSeNet (resnet18, OS 16, SOLVER.AUX True) cost on one GPU: warmed, device-synchronised eager
+timings of the HIP model and of tests/_bisenet_oracle.py — the same network on torch's own device
+kernels, which is what PyTorch-ROCm gives a user today — one JSON line.
+
+  train  ms/step (forward + MixSoftmaxCrossEntropyLoss + backward) at 8 x 3 x 768 x 768
+  eval   ms/forward at 1 x 3 x 1024 x 2048 and 8 x 3 x 1024 x 2048
+  gate   ms per forward + backward of functional.channel_gate alone (plain input, one-layer
+         branch) against its torch composition at [8,96,96,256] and [8,48,48,128]
+
+each in fp32 and bf16 (the torch baseline under torch.autocast(bfloat16)).  Every leg runs in a
+child process of its own under a time limit; the first leg that fails ends the run.
+
+    python tools/bisenet_bench.py [--steps 10] [--warmup 3] [--dtypes bf16,fp32]
+                                  [--legs train,eval1,eval8,gate] [--out FILE]
+
+Weights are synthesised (oracle.synth); timings do not depend on them.  Per-kernel times:
+`rocprofv3 --kernel-trace --stats -- python tools/bisenet_bench.py --leg train --dtype bf16
+--impl hip --steps 3 --warmup 1` (profiles/bisenet.md).
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+SHAPES = {"train": (8, 768, 768), "eval1": (1, 1024, 2048), "eval8": (8, 1024, 2048)}
+GATE_SHAPES = ((8, 96, 96, 256), (8, 48, 48, 128))
+LEG_TIMEOUT = 420  # seconds per child
+
+
+def timed(fn, steps, warmup):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def build_hip(dtype):
+    import torch.nn as nn
+    import segmentron_amd
+    from oracle import synth
+    from segmentron_amd.config import cfg, reset_cfg
+    reset_cfg()
+    cfg.update_from_list(["DATASET.NAME", "cityscape", "MODEL.MODEL_NAME", "BiSeNet",
+                          "MODEL.BACKBONE", "resnet18", "MODEL.OUTPUT_STRIDE", "16", "SOLVER.AUX",
+                          "True", "TRAIN.BACKBONE_PRETRAINED", "False"])
+    cfg.PHASE = "train"
+    cfg.check_and_freeze()
+    segmentron_amd.set_compute_dtype(dtype)
+    model = segmentron_amd.get_segmentation_model()
+    sd = synth.synth_like(model.state_dict(), seed=0, conditioned=True)
+    model.load_state_dict(sd)
+    reset_cfg()
+    for m in model.modules():
+        if isinstance(m, nn.Dropout):
+            m.p = 0.0
+    return model.cuda(), sd
+
+
+def model_leg(leg, impl, dtype, steps, warmup):
+    import torch
+    import torch.nn.functional as TF
+    import _bisenet_oracle as O
+    from oracle import synth, torch_ref
+    B, H, W = SHAPES[leg]
+    x = synth.synth_images(B, H, W, seed=0).cuda()
+    y = synth.synth_targets(B, H, W, seed=0).cuda()
+    model, sd = build_hip(dtype)
+    bf16 = dtype == torch.bfloat16
+    if impl == "hip":
+        if leg == "train":
+            model.train()
+
+            def step():
+                model.zero_grad(set_to_none=True)
+                outs = model(x)
+                loss = TF.cross_entropy(outs[0], y, ignore_index=-1)
+                for o in outs[1:]:
+                    loss = loss + O.AUX_WEIGHT * TF.cross_entropy(o, y, ignore_index=-1)
+                loss.backward()
+        else:
+            model.eval()
+
+            def step():
+                with torch.no_grad():
+                    model(x)
+    else:
+        del model
+        s = torch_ref.clone_state({k: v.cuda() for k, v in sd.items()}, requires_grad=leg == "train")
+        net = torch_ref.OracleNet(s, training=leg == "train", drop_p=0.0, aux=True)
+        params = [v for v in s.values() if v.requires_grad]
+
+        def step():
+            for p in params:
+                p.grad = None
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
+                if leg == "train":
+                    torch_ref.mix_softmax_ce(O.forward(net, x), y, O.AUX_WEIGHT, -1).backward()
+                else:
+                    with torch.no_grad():
+                        O.forward(net, x)
+    return timed(step, steps, warmup)
+
+
+def gate_leg(impl, dtype, steps, warmup):
+    """channel_gate(x, one 1x1 conv + BN + ReLU branch) forward + backward on a plain input."""
+    import torch
+    import torch.nn.functional as TF
+    import segmentron_amd
+    from segmentron_amd import functional as F
+    from segmentron_amd.modules import _ConvBNReLU
+    segmentron_amd.set_compute_dtype(dtype)
+    out = {}
+    for N, H, W, C in GATE_SHAPES:
+        br = _ConvBNReLU(C, C, 1).cuda().train()
+        x = torch.randn(N, H, W, C, device="cuda").to(dtype).requires_grad_()
+        g = torch.randn(N, H, W, C, device="cuda").to(dtype)
+        if impl == "hip":
+            def step():
+                x.grad = None
+                F.channel_gate(F.Act(x), br, identity=False).backward(g)
+        else:
+            xc, gc = x.detach().permute(0, 3, 1, 2).requires_grad_(), g.permute(0, 3, 1, 2)
+            w, bn = br.conv.weight, br.bn
+
+            def step():
+                xc.grad = None
+                a = TF.conv2d(TF.adaptive_avg_pool2d(xc.float(), 1), w)
+                a = TF.relu(TF.batch_norm(a, None, None, bn.weight, bn.bias, True))
+                (xc * torch.sigmoid(a).to(xc.dtype)).backward(gc)
+        out["%dx%dx%dx%d" % (N, H, W, C)] = round(timed(step, steps, warmup), 4)
+    return out
+
+
+def child(args):
+    import torch
+    dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}[args.dtype]
+    if args.leg == "gate":
+        val = gate_leg(args.impl, dtype, args.steps, args.warmup)
+    else:
+        val = round(model_leg(args.leg, args.impl, dtype, args.steps, args.warmup), 3)
+    print("RESULT " + json.dumps({"leg": args.leg, "impl": args.impl, "dtype": args.dtype,
+                                  "ms": val, "device": torch.cuda.get_device_name(0)}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dtypes", default="bf16,fp32")
+    ap.add_argument("--legs", default="train,eval1,eval8,gate")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--leg", default=None, help="(child) run this one leg in this process")
+    ap.add_argument("--impl", default="hip", choices=["hip", "torch"])
+    ap.add_argument("--dtype", default="bf16")
+    args = ap.parse_args()
+    if args.leg:
+        return child(args)
+    res = {"steps": args.steps, "warmup": args.warmup, "shapes": SHAPES, "ms": {}}
+    for leg in args.legs.split(","):
+        for dn in args.dtypes.split(","):
+            for impl in ("hip", "torch"):
+                cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--impl", impl,
+                       "--dtype", dn, "--steps", str(args.steps), "--warmup", str(args.warmup)]
+                try:
+                    p = subprocess.run(cmd, capture_output=True, text=True, timeout=LEG_TIMEOUT)
+                except subprocess.TimeoutExpired:
+                    sys.stderr.write("leg %s/%s/%s ran past %d s: stopping\n"
+                                     % (leg, impl, dn, LEG_TIMEOUT))
+                    return 124
+                line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+                if p.returncode != 0 or not line:  # nothing more is started on the GPU
+                    sys.stderr.write("leg %s/%s/%s failed (%d): stopping\n%s\n"
+                                     % (leg, impl, dn, p.returncode, p.stderr[-2000:]))
+                    return p.returncode or 1
+                r = json.loads(line[0][len("RESULT "):])
+                res["device"] = r["device"]
+                res["ms"]["%s/%s/%s" % (leg, impl, dn)] = r["ms"]
+                sys.stderr.write("%s/%s/%s: %s\n" % (leg, impl, dn, r["ms"]))
+    text = json.dumps(res)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
