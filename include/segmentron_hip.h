@@ -125,6 +125,17 @@ int seg_dwconv3x3_bwd_fused_add(int dtype, const void* dy, long lddy, const void
                                 const float* pro_scale, const float* pro_shift, const void* res,
                                 long ldr, void* g, long ldg, float* partial_w, float* partial_bn,
                                 int grid_y, void* stream);
+/* seg_dwconv3x3_bwd_fused_add with the masked gradient rounded to dtype before res joins: bit for
+ * bit seg_sum_n over the stored g of seg_dwconv3x3_bwd_fused and res, in one pass — for a res that
+ * used to meet g in that sum (the shortcut conv's data gradient of a conv-skip Xception block).
+ * Sliding family only: seg_dwconv3x3_bwd_fused_sum_ok (dilation 1, C a multiple of 4 and of the
+ * element type's 16-byte vector), pure host. */
+int seg_dwconv3x3_bwd_fused_sum_ok(int dtype, int C, int dil);
+int seg_dwconv3x3_bwd_fused_sum(int dtype, const void* dy, long lddy, const void* x, long ldx, int N,
+                                int H, int W, int C, const float* w9c, int w_layout, int pro_mode,
+                                const float* pro_scale, const float* pro_shift, const void* res,
+                                long ldr, void* g, long ldg, float* partial_w, float* partial_bn,
+                                int grid_y, void* stream);
 
 /* ---- nn.BatchNorm2d / nn.SyncBatchNorm (train + eval, forward + backward) -------------------
  * Replaces F.batch_norm behind every `bn*` module (segmentron/modules/basic.py:41,43,70;
@@ -249,6 +260,17 @@ int seg_bn_bwd_apply(int dtype, const void* g, long ldg, const void* x, long ldx
                      const float* scale, const float* shift, const float* c0, const float* c1,
                      const float* chan_mul, long rows_per_n, const void* elem_mul, long ldm,
                      void* dx, long lddx, long M, int C, void* stream);
+/* dx = round(scale*g' - c0 - c1*x) + round(dx_add): `add` ([M][C] of dtype, pitch ldadd) is the
+ * gradient of another consumer of the same raw tensor.  add_mode 0: dx_add = add (already w.r.t.
+ * the raw tensor).  Otherwise add is w.r.t. that consumer's activated input (add_mode = its
+ * prologue bits on the same scale / shift) and dx_add = scale*mask(add) - add_c0 - add_c1*x with the
+ * coefficients of ITS finalize (null: evaluation mode).  Both terms are rounded to dtype first, so
+ * the result equals the separate seg_bn_bwd_apply passes + seg_sum_n bit for bit.  Geometry of
+ * seg_bn_bwd_apply. */
+int seg_bn_bwd_apply_add(int dtype, const void* g, long ldg, const void* x, long ldx, int mode,
+                         const float* scale, const float* shift, const float* c0, const float* c1,
+                         const void* add, long ldadd, int add_mode, const float* add_c0,
+                         const float* add_c1, void* dx, long lddx, long M, int C, void* stream);
 
 /* ---- nn.GroupNorm(min(32, C), C): the 'GN' choice of cfg.MODEL.BN_TYPE -------------------------
  * Replaces the nn.GroupNorm modules segmentron/modules/batch_norm.py:105-108,129 builds (F.group_norm

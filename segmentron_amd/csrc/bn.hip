@@ -260,6 +260,8 @@ struct BwdArgs {
   const float* scale; const float* shift; const float* c0; const float* c1;
   const float* chan_mul; long rows_per_n;
   const void* elem_mul; long ldm;
+  // bn_bwd_apply_kernel<T, true>: a second gradient of type T joins dx (see the kernel)
+  const void* add; long ldadd; int add_mode; const float* add_c0; const float* add_c1;
   float* partial;  // [gridDim.y][2][C]
   long ldg, ldx, lddx;
   long M; int C, CV;
@@ -386,7 +388,14 @@ __global__ void bn_bwd_finalize_kernel(const double* __restrict__ sums, double c
   c0_o[c] = (float)(s * m1 - c1 * mu);
 }
 
-template <typename T>
+// ADD: dx = round(dx) + round(dx_add) — `add` is the gradient another consumer of the same raw
+// tensor parked (a forked activation: functional.GradFork).  add_mode 0: it is already w.r.t. the
+// raw tensor, dx_add = add.  Otherwise it is w.r.t. that consumer's activated input and takes its
+// own BatchNorm backward here, on the same scale / shift: dx_add = scale * mask(add) - c0' - c1' * x
+// (add_mode = that consumer's prologue bits, add_c0 / add_c1 from ITS finalize).  Both terms are
+// rounded to T before they are added: the result equals the separate apply passes followed by the
+// 2-ary gradient sum (seg_sum_n) bit for bit, in one pass.
+template <typename T, bool ADD>
 __global__ __launch_bounds__(EW_MAX_THREADS) void bn_bwd_apply_kernel(const BwdArgs a) {
   constexpr int VEC = Vec<T>::N;
   const int cvb = a.lpr, rpb = a.rpb;
@@ -396,9 +405,10 @@ __global__ __launch_bounds__(EW_MAX_THREADS) void bn_bwd_apply_kernel(const BwdA
   const int c0 = cv * VEC;
   const T* __restrict__ G = reinterpret_cast<const T*>(a.g);
   const T* __restrict__ X = reinterpret_cast<const T*>(a.x);
+  const T* __restrict__ AD = reinterpret_cast<const T*>(a.add);
   T* __restrict__ DX = reinterpret_cast<T*>(a.dx);
-  float sc[VEC], sh[VEC], k0[VEC], k1[VEC];
-  load_affine<VEC>(a.mode, a.scale, a.shift, c0, sc, sh);
+  float sc[VEC], sh[VEC], k0[VEC], k1[VEC], j0[VEC], j1[VEC];
+  load_affine<VEC>(a.mode | (ADD ? a.add_mode : 0), a.scale, a.shift, c0, sc, sh);
   if (a.c0) {
     load_params<VEC>(a.c0, c0, k0);
     load_params<VEC>(a.c1, c0, k1);
@@ -406,12 +416,23 @@ __global__ __launch_bounds__(EW_MAX_THREADS) void bn_bwd_apply_kernel(const BwdA
 #pragma unroll
     for (int k = 0; k < VEC; ++k) k0[k] = k1[k] = 0.f;
   }
+  if (ADD && a.add_c0) {
+    load_params<VEC>(a.add_c0, c0, j0);
+    load_params<VEC>(a.add_c1, c0, j1);
+  } else {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) j0[k] = j1[k] = 0.f;
+  }
   const int M = (int)a.M, tile = rpb * EW_UN, step = gridDim.y * tile;
   for (int base = blockIdx.y * tile + sy; base < M; base += step) {
     BwdRaw<T> raw[EW_UN];
+    uint4 radd[EW_UN];
 #pragma unroll
-    for (int u = 0; u < EW_UN; ++u)
-      load_bwd_raw<T>(a, G, X, min(base + u * rpb, M - 1), c0, raw[u]);
+    for (int u = 0; u < EW_UN; ++u) {
+      const int row = min(base + u * rpb, M - 1);
+      load_bwd_raw<T>(a, G, X, row, c0, raw[u]);
+      if (ADD) radd[u] = ldg16(AD + (long)row * a.ldadd + c0);
+    }
 #pragma unroll
     for (int u = 0; u < EW_UN; ++u) {
       const int row = base + u * rpb;
@@ -421,6 +442,26 @@ __global__ __launch_bounds__(EW_MAX_THREADS) void bn_bwd_apply_kernel(const BwdA
       if (a.mode & PRO_AFFINE) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) g[k] = g[k] * sc[k] - k0[k] - k1[k] * x[k];
+      }
+      if (ADD) {
+        float ad[VEC], gr[VEC];
+        Vec<T>::unpack(radd[u], ad);
+        if (a.add_mode & PRO_RELU) {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            const float y = (a.add_mode & PRO_AFFINE) ? fmaf(x[k], sc[k], sh[k]) : x[k];
+            const bool on = y > 0.f && (!(a.add_mode & PRO_CLAMP6) || y < 6.f);
+            ad[k] = on ? ad[k] : 0.f;
+          }
+        }
+        if (a.add_mode & PRO_AFFINE) {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) ad[k] = ad[k] * sc[k] - j0[k] - j1[k] * x[k];
+        }
+        Vec<T>::unpack(Vec<T>::pack(ad), ad);
+        Vec<T>::unpack(Vec<T>::pack(g), gr);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) g[k] = gr[k] + ad[k];
       }
       stg16(DX + (long)row * a.lddx + c0, Vec<T>::pack(g));
     }
@@ -1060,6 +1101,7 @@ extern "C" int seg_bn_bwd_reduce(int dtype, const void* g, long ldg, const void*
   a.g = g; a.x = x; a.dx = nullptr; a.scale = scale; a.shift = shift; a.c0 = nullptr; a.c1 = nullptr;
   a.chan_mul = chan_mul; a.rows_per_n = rows_per_n > 0 ? rows_per_n : 1;
   a.elem_mul = elem_mul; a.ldm = ldm;
+  a.add = nullptr; a.ldadd = 0; a.add_mode = 0; a.add_c0 = a.add_c1 = nullptr;
   a.partial = partial; a.ldg = ldg; a.ldx = ldx; a.lddx = 0; a.M = M; a.C = C; a.CV = C / vec;
   a.mode = mode;
   const EwGeom geo = ew_geom(a.CV);
@@ -1128,34 +1170,66 @@ extern "C" int seg_bn_bwd_finalize_s(const double* sums, double count, const dou
 
 // dx = scale * g' - c0 - c1 * x   (mode has AFFINE);  dx = g'  (mode without AFFINE: plain ReLU
 // backward / dropout-mask backward).  c0/c1 null with AFFINE -> eval-mode BN backward (scale only).
+namespace seg {
+static int bn_bwd_apply_launch(const char* name, int dtype, const void* g, long ldg, const void* x,
+                               long ldx, int mode, const float* scale, const float* shift,
+                               const float* c0, const float* c1, const float* chan_mul,
+                               long rows_per_n, const void* elem_mul, long ldm, const void* add,
+                               long ldadd, int add_mode, const float* add_c0,
+                               const float* add_c1, void* dx, long lddx, long M, int C,
+                               void* stream) {
+  const int vec = dtype == DT_BF16 ? 8 : 4;
+  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "%s: bad dtype %d", name, dtype);
+  SEG_REQUIRE(C % vec == 0 && ldg % vec == 0 && ldx % vec == 0 && lddx % vec == 0 &&
+                  ldadd % vec == 0,
+              "%s: C/ld must be multiples of %d", name, vec);
+  SEG_REQUIRE(((mode & PRO_AFFINE) == 0) || (scale && shift), "%s: missing scale/shift", name);
+  BwdArgs a;
+  a.g = g; a.x = x; a.dx = dx; a.scale = scale; a.shift = shift; a.c0 = c0; a.c1 = c1;
+  a.chan_mul = chan_mul; a.rows_per_n = rows_per_n > 0 ? rows_per_n : 1;
+  a.elem_mul = elem_mul; a.ldm = ldm;
+  a.add = add; a.ldadd = ldadd; a.add_mode = add_mode; a.add_c0 = add_c0; a.add_c1 = add_c1;
+  SEG_REQUIRE(((add_mode & PRO_AFFINE) == 0) || (scale && shift), "%s: missing scale/shift", name);
+  SEG_REQUIRE((add_c0 == nullptr) == (add_c1 == nullptr), "%s: add_c0 / add_c1 go together", name);
+  a.partial = nullptr; a.ldg = ldg; a.ldx = ldx; a.lddx = lddx; a.M = M; a.C = C; a.CV = C / vec;
+  a.mode = mode;
+  SEG_REQUIRE(M < (1L << 31), "%s: M overflows int", name);
+  const EwGeom geo = ew_geom(a.CV);
+  a.lpr = geo.lpr; a.rpb = geo.rpb;
+  const dim3 grid = ew_grid2(geo, M);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == DT_BF16) {
+    if (add) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true>), grid, dim3(geo.threads), 0, st, a);
+    else hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false>), grid, dim3(geo.threads), 0, st, a);
+  } else {
+    if (add) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), grid, dim3(geo.threads), 0, st, a);
+    else hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false>), grid, dim3(geo.threads), 0, st, a);
+  }
+  return check_launch(name);
+}
+}  // namespace seg
+
 extern "C" int seg_bn_bwd_apply(int dtype, const void* g, long ldg, const void* x, long ldx,
                                 int mode, const float* scale, const float* shift, const float* c0,
                                 const float* c1, const float* chan_mul, long rows_per_n,
                                 const void* elem_mul, long ldm, void* dx, long lddx, long M, int C,
                                 void* stream) {
-  using namespace seg;
-  const int vec = dtype == DT_BF16 ? 8 : 4;
-  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "bn_bwd_apply: bad dtype %d", dtype);
-  SEG_REQUIRE(C % vec == 0 && ldg % vec == 0 && ldx % vec == 0 && lddx % vec == 0,
-              "bn_bwd_apply: C/ld must be multiples of %d", vec);
-  SEG_REQUIRE(((mode & PRO_AFFINE) == 0) || (scale && shift), "bn_bwd_apply: missing scale/shift");
-  BwdArgs a;
-  a.g = g; a.x = x; a.dx = dx; a.scale = scale; a.shift = shift; a.c0 = c0; a.c1 = c1;
-  a.chan_mul = chan_mul; a.rows_per_n = rows_per_n > 0 ? rows_per_n : 1;
-  a.elem_mul = elem_mul; a.ldm = ldm;
-  a.partial = nullptr; a.ldg = ldg; a.ldx = ldx; a.lddx = lddx; a.M = M; a.C = C; a.CV = C / vec;
-  a.mode = mode;
-  SEG_REQUIRE(M < (1L << 31), "bn_bwd_apply: M overflows int");
-  const EwGeom geo = ew_geom(a.CV);
-  a.lpr = geo.lpr; a.rpb = geo.rpb;
-  const dim3 grid = ew_grid2(geo, M);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t>), grid, dim3(geo.threads), 0,
-                       (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<float>), grid, dim3(geo.threads), 0,
-                       (hipStream_t)stream, a);
-  return check_launch("bn_bwd_apply");
+  return seg::bn_bwd_apply_launch("bn_bwd_apply", dtype, g, ldg, x, ldx, mode, scale, shift, c0, c1,
+                                  chan_mul, rows_per_n, elem_mul, ldm, nullptr, 0, 0, nullptr,
+                                  nullptr, dx, lddx, M, C, stream);
+}
+
+// ... + a second gradient `add`: [M][C] of `dtype`, pitch ldadd, see bn_bwd_apply_kernel (the
+// launch geometry of seg_bn_bwd_apply).  dx may alias g.
+extern "C" int seg_bn_bwd_apply_add(int dtype, const void* g, long ldg, const void* x, long ldx,
+                                    int mode, const float* scale, const float* shift,
+                                    const float* c0, const float* c1, const void* add, long ldadd,
+                                    int add_mode, const float* add_c0, const float* add_c1,
+                                    void* dx, long lddx, long M, int C, void* stream) {
+  SEG_REQUIRE(add != nullptr, "bn_bwd_apply_add: add must be non-null");
+  return seg::bn_bwd_apply_launch("bn_bwd_apply_add", dtype, g, ldg, x, ldx, mode, scale, shift, c0,
+                                  c1, nullptr, 0, nullptr, 0, add, ldadd, add_mode, add_c0, add_c1,
+                                  dx, lddx, M, C, stream);
 }
 
 // Fused (non-sync) variants: partial rows [R][2][C] fp32 straight from the conv / reduce kernels.

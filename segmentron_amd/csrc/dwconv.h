@@ -37,7 +37,8 @@ int launch_dw_slide_fwd(int dtype, const void* x, long ldx, int N, int H, int W,
 int launch_dw_slide_bwd(int dtype, const void* dy, long lddy, const void* x, long ldx, int N, int H,
                         int W, int C, const float* w, int w_layout, int pro_mode, const float* sc,
                         const float* sh, void* g, long ldg, float* partial_w, float* partial_bn,
-                        int rows, hipStream_t st, const void* res = nullptr, long ldr = 0);
+                        int rows, hipStream_t st, const void* res = nullptr, long ldr = 0,
+                        int res_mode = 1);  // 1: g + res, one rounding; 2: as the 2-ary sum
 // ---- LDS-tiled, stride 1, dilation 1/2
 int dw_tiled_grid_y(int dtype, int C, int N, int H, int W, int kind);
 int launch_dw_tiled(int dtype, const void* x, long ldx, int N, int H, int W, int C,

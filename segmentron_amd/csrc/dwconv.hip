@@ -476,6 +476,7 @@ static int strip_gx(int CV, int& cvb_log2) {
 //                          1       3..64   row-chain   v (C, lddy), 4    [9][C]
 //                          1       > 64    strip       4                 [9][C]
 //   ... with residual      1       1       sliding     v (ldr: 4)        torch or [9][C]
+//       (one rounding, or — sliding family only — with the arithmetic of the 2-ary sum it replaces)
 //   weight gradient        1       1, 2    tiled       v                 -
 //                          other           strip       v                 -
 //
@@ -634,12 +635,15 @@ extern "C" int seg_dwconv3x3_wgrad(int dtype, const void* x, long ldx, int N, in
 // With `res` ([N,H,W,C], pitch ldr, element type of g; the _add entry): that tensor is added to the
 // masked data gradient in the store path, g = relu_mask(x) * dgrad + res.  Dilation 1 only — the
 // caller does a separate add otherwise (seg_dwconv3x3_bwd_fused_add_ok).
+// res_mode 2 (the _sum entry): the masked data gradient is rounded to the storage type before
+// `res` joins — the stored g of the launch without `res` followed by seg_sum_n, in one pass.
+// Sliding family only (seg_dwconv3x3_bwd_fused_sum_ok).
 namespace seg {
 static int dw_bwd_fused(const char* name, int dtype, const void* dy, long lddy, const void* x,
                         long ldx, int N, int H, int W, int C, const float* w9c, int w_layout,
                         int dil, int pro_mode, const float* pro_scale, const float* pro_shift,
                         const void* res, long ldr, void* g, long ldg, float* partial_w,
-                        float* partial_bn, int grid_y, hipStream_t st) {
+                        float* partial_bn, int grid_y, hipStream_t st, int res_mode = 1) {
   const int vec = 4;  // HVec: 4 channels per thread in both element types
   SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "%s: bad dtype %d", name, dtype);
   const DwRoute r = dw_route(res ? DW_OP_BWD_ADD : DW_OP_BWD, dtype, C, 1, dil);
@@ -656,11 +660,13 @@ static int dw_bwd_fused(const char* name, int dtype, const void* dy, long lddy, 
   SEG_REQUIRE(C % r.vec == 0 && lddy % r.vec == 0 &&
                   (r.family == DW_ROW || (ldx % r.vec == 0 && ldg % r.vec == 0)),
               "%s: C/ld must be multiples of %d", name, r.vec);
+  SEG_REQUIRE(res_mode == 1 || r.family == DW_SLIDE,
+              "%s: only the sliding kernels take residual mode %d", name, res_mode);
   switch (r.family) {
     case DW_SLIDE:
       return launch_dw_slide_bwd(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, w_layout, pro_mode,
                                  pro_scale, pro_shift, g, ldg, partial_w, partial_bn, grid_y, st,
-                                 res, ldr);
+                                 res, ldr, res_mode);
     case DW_TILED:
       return launch_dw_bwd_tiled(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, w_layout, dil, pro_mode,
                                  pro_scale, pro_shift, g, ldg, partial_w, partial_bn, grid_y, st,
@@ -701,6 +707,30 @@ extern "C" int seg_dwconv3x3_bwd_fused_add(int dtype, const void* dy, long lddy,
   return seg::dw_bwd_fused("dwconv3x3_bwd_fused_add", dtype, dy, lddy, x, ldx, N, H, W, C, w9c,
                            w_layout, 1, pro_mode, pro_scale, pro_shift, res, ldr, g, ldg, partial_w,
                            partial_bn, grid_y, (hipStream_t)stream);
+}
+
+// Does a fused backward with a residual of C channels of `dtype` run on the sliding family — the
+// one seg_dwconv3x3_bwd_fused_sum needs?  Pure host.
+extern "C" int seg_dwconv3x3_bwd_fused_sum_ok(int dtype, int C, int dil) {
+  using namespace seg;
+  if ((dtype != DT_F32 && dtype != DT_BF16) || C < 1 || dil < 1) return 0;
+  const DwRoute r = dw_route(DW_OP_BWD_ADD, dtype, C, 1, dil);
+  return r.family == DW_SLIDE && C % r.vec == 0 ? 1 : 0;
+}
+
+// seg_dwconv3x3_bwd_fused_add with the masked gradient rounded to `dtype` before res joins: bit for
+// bit seg_sum_n over the stored g of seg_dwconv3x3_bwd_fused and res, in one pass (fp32: the same
+// values as the _add entry).
+extern "C" int seg_dwconv3x3_bwd_fused_sum(int dtype, const void* dy, long lddy, const void* x,
+                                           long ldx, int N, int H, int W, int C, const float* w9c,
+                                           int w_layout, int pro_mode, const float* pro_scale,
+                                           const float* pro_shift, const void* res, long ldr,
+                                           void* g, long ldg, float* partial_w, float* partial_bn,
+                                           int grid_y, void* stream) {
+  SEG_REQUIRE(res != nullptr, "dwconv3x3_bwd_fused_sum: res must be non-null");
+  return seg::dw_bwd_fused("dwconv3x3_bwd_fused_sum", dtype, dy, lddy, x, ldx, N, H, W, C, w9c,
+                           w_layout, 1, pro_mode, pro_scale, pro_shift, res, ldr, g, ldg, partial_w,
+                           partial_bn, grid_y, (hipStream_t)stream, 2);
 }
 
 extern "C" int seg_dwconv3x3_bwd_fused(int dtype, const void* dy, long lddy, const void* x,

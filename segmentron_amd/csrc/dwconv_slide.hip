@@ -417,11 +417,17 @@ __global__ __launch_bounds__(SL_THREADS, SL_OCC_F) void dwconv_slide_fwd_kernel(
 }
 
 // ------------------------------------------------------------------------------ fused backward
-//   g'[q]   = relu_mask(x[q]) * sum_k dy[q - d_k] * w[k]   (+ res[q])
+//   g'[q]   = relu_mask(x[q]) * sum_k dy[q - d_k] * w[k]
 //   dW[k]  += act(x[q]) * dy[q - d_k]                       the same shifted dy values
-//   (sum g', sum g' * x_raw)                                of the masked gradient before `res`
+//   (sum g', sum g' * x_raw)                                in fp32, never of `res`
+// `res` (a gradient w.r.t. the tensor the ReLU reads) only enters the stored value:
+//   SL_RES_NONE  stores g'
+//   SL_RES_POST  stores g' + res, one rounding
+//   SL_RES_SUM   stores round(g') + res: g' is rounded to the storage type first — bit for bit the
+//                separate 2-ary sum of the stored g' and `res` (seg_sum_n) that the launch replaces
 // The window holds dy (no activation); window position (a, b) pairs with tap 8 - (3a + b).
-template <typename T, int MODE, bool RES, bool XCHG>
+enum { SL_RES_NONE = 0, SL_RES_POST = 1, SL_RES_SUM = 2 };
+template <typename T, int MODE, int RES, bool XCHG>
 __global__ __launch_bounds__(SL_THREADS, 2) void dwconv_slide_bwd_kernel(const DwSlideArgs a) {
   using IO = SlIO<T>;
   using raw_t = typename IO::raw_t;
@@ -499,11 +505,12 @@ __global__ __launch_bounds__(SL_THREADS, 2) void dwconv_slide_bwd_kernel(const D
       g.lo.x = on(xa.lo.x) ? g.lo.x : 0.f; g.lo.y = on(xa.lo.y) ? g.lo.y : 0.f;
       g.hi.x = on(xa.hi.x) ? g.hi.x : 0.f; g.hi.y = on(xa.hi.y) ? g.hi.y : 0.f;
     }
-    if (RES) {
+    if (RES == SL_RES_POST || RES == SL_RES_SUM) {
       const Q4 rr = IO::unpack(rraw);
+      const Q4 gs = RES == SL_RES_SUM ? IO::unpack(IO::pack(g)) : g;
       Q4 o;
-      o.lo = g.lo + rr.lo;
-      o.hi = g.hi + rr.hi;
+      o.lo = gs.lo + rr.lo;
+      o.hi = gs.hi + rr.hi;
       sl_st_row<raw_t>(Gb + (long)ro * gpitch, (unsigned)gpitch, goff, IO::pack(o));
     } else {
       sl_st_row<raw_t>(Gb + (long)ro * gpitch, (unsigned)gpitch, goff, IO::pack(g));
@@ -651,7 +658,7 @@ static void slide_launch_fwd(const DwSlideArgs& a, dim3 grid, hipStream_t st) {
     default: break;
   }
 }
-template <typename T, bool RES>
+template <typename T, int RES>
 static void slide_launch_bwd(const DwSlideArgs& a, dim3 grid, hipStream_t st) {
   const bool xc = slide_exchange(a, (int)sizeof(T));
   switch (a.pro_mode) {
@@ -693,7 +700,7 @@ int launch_dw_slide_fwd(int dtype, const void* x, long ldx, int N, int H, int W,
 int launch_dw_slide_bwd(int dtype, const void* dy, long lddy, const void* x, long ldx, int N, int H,
                         int W, int C, const float* w, int w_layout, int pro_mode, const float* sc,
                         const float* sh, void* g, long ldg, float* partial_w, float* partial_bn,
-                        int rows, hipStream_t st, const void* res, long ldr) {
+                        int rows, hipStream_t st, const void* res, long ldr, int res_mode) {
   DwSlideArgs a;
   a.x = x; a.dy = dy; a.res = res; a.y = g; a.w = w; a.w_layout = w_layout & 1;
   a.sc = sc; a.sh = sh; a.partial = partial_w; a.partial_bn = partial_bn;
@@ -708,12 +715,16 @@ int launch_dw_slide_bwd(int dtype, const void* dy, long lddy, const void* x, lon
               "dwconv bwd (slide): %d partial rows, the launch writes %d (seg_dwconv_grid_y)", rows,
               N * a.nstrips * a.nwblk);
   const dim3 grid((unsigned)((long)a.ncblk * a.nwblk * a.nstrips * N));
+  const int rm = !res ? SL_RES_NONE : res_mode;
+  SEG_REQUIRE(rm >= SL_RES_NONE && rm <= SL_RES_SUM, "dwconv bwd (slide): residual mode %d", rm);
   if (dtype == DT_BF16) {
-    if (res) slide_launch_bwd<bf16_t, true>(a, grid, st);
-    else slide_launch_bwd<bf16_t, false>(a, grid, st);
+    if (rm == SL_RES_SUM) slide_launch_bwd<bf16_t, SL_RES_SUM>(a, grid, st);
+    else if (rm == SL_RES_POST) slide_launch_bwd<bf16_t, SL_RES_POST>(a, grid, st);
+    else slide_launch_bwd<bf16_t, SL_RES_NONE>(a, grid, st);
   } else {
-    if (res) slide_launch_bwd<float, true>(a, grid, st);
-    else slide_launch_bwd<float, false>(a, grid, st);
+    if (rm == SL_RES_SUM) slide_launch_bwd<float, SL_RES_SUM>(a, grid, st);
+    else if (rm == SL_RES_POST) slide_launch_bwd<float, SL_RES_POST>(a, grid, st);
+    else slide_launch_bwd<float, SL_RES_NONE>(a, grid, st);
   }
   return check_launch("dwconv3x3_bwd_fused (slide)");
 }

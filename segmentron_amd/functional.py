@@ -42,10 +42,13 @@ RELU, RELU6 = 1, 5  # values of `Act.relu`: prologue / mask bits (ReLU6 = relu +
 class Act:
     """NHWC activation with a pending BatchNorm affine and/or ReLU (`relu` in {0/False, 1/True,
     RELU6})."""
-    __slots__ = ("t", "bn", "relu")
+    __slots__ = ("t", "bn", "relu", "park")
 
-    def __init__(self, t, bn=None, relu=False):
+    def __init__(self, t, bn=None, relu=False, park=None):
         self.t, self.bn, self.relu = t, bn, relu
+        # a GradFork (kind RAW) the 1x1 convolution that consumes this alias may park its input
+        # gradient in (conv_bn): the low-level feature that leaves an Xception block
+        self.park = park
 
     @property
     def pro(self):
@@ -79,15 +82,40 @@ class GradFork:
     (2 reads + 1 write of the tensor, 25 launches per C3 step).  The identity consumer's backward
     (`_ApplyFn`) parks ITS gradient here and reports none; the depthwise backward of the other
     consumer (`_DwFn`), which autograd can only run later (its output feeds the sum), adds the
-    parked tensor in its store path and returns the total."""
-    __slots__ = ("g",)
+    parked tensor in its store path and returns the total.
 
-    def __init__(self):
-        self.g = None
+    The same hand-off serves the other forks whose last consumer in backward is a depthwise conv
+    (`kind` says what the parked gradient is taken with respect to, hence where the taker adds it):
+      POST  the plain forked tensor — after the taker's ReLU mask, in the store only, one
+            rounding: the identity path above;
+      SUM   the same for the shortcut conv of a conv-skip block with a plain input, with the
+            arithmetic of the 2-ary sum it replaces (the masked gradient is rounded first);
+      PRE   the ACTIVATED input both consumers read through the same pending BatchNorm + ReLU
+            (the first block's input): the shortcut conv runs its BatchNorm-backward reduce and
+            finalize, parks its bare data gradient with the coefficients (`coef` = prologue bits,
+            c0, c1) and reports dgamma / dbeta only; the taker's bn_bwd_apply, its last pass, does
+            the shortcut's apply on the way and adds the two;
+      RAW   the raw tensor under a pending BatchNorm (the low-level feature: a folded 1x1 conv's
+            dx): added by the taker's bn_bwd_apply.
+    SUM, PRE and RAW reproduce the separate passes + `fork`'s sum bit for bit: the hand-off
+    removes passes over the tensors, not roundings.  The aliases still come from `fork`: a consumer that does not park returns its gradient as
+    ever and the n-ary sum adds it.  A gradient is parked only into an empty slot and only while
+    the taker has not run (`closed`), and taken exactly once.  The taker must take part in the
+    backward pass whenever the parker does (both feed the block's output; for RAW: the block's
+    output reaches the loss)."""
+    __slots__ = ("g", "kind", "closed", "coef")
+    POST, PRE, RAW, SUM = 0, 1, 2, 3
+
+    def __init__(self, kind=0):
+        self.g, self.kind, self.closed, self.coef = None, kind, False, None
 
     def take(self):
         g, self.g = self.g, None
         return g
+
+    def can_park(self, kind, g, like):
+        return (self.kind == kind and self.g is None and not self.closed
+                and g.dtype == like.dtype and tuple(g.shape) == tuple(like.shape))
 
 
 def uses_batch_stats(bn):
@@ -514,6 +542,7 @@ class ConvSpec:
         self.partial = None
         self.drop_bias = False
         self.fork = None
+        self.park = None  # GradFork this conv parks its input gradient in (fork: takes from)
 
 
 class _ConvFn(torch.autograd.Function):
@@ -592,6 +621,19 @@ class _ConvFn(torch.autograd.Function):
                                  lambda: pack_conv_weight_tconv(weight, Op, dt))
                 g, _ = K.conv_gemm(dy_full, wt, Cw, KH, KW, s.stride, s.pad, s.dil,
                                    tconv_out_hw=(x.shape[1], x.shape[2]))
+            p = s.park
+            if res is None and p is not None and p.kind in (GradFork.SUM, GradFork.PRE) \
+                    and p.can_park(p.kind, g, x):
+                # the bare data gradient goes to the fork's other consumer, a depthwise backward,
+                # which adds it in its own passes (GradFork SUM / PRE)
+                if p.kind == GradFork.PRE:
+                    bn = s.bn_in
+                    mode = PRO_AFFINE | int(s.relu)
+                    partial = K.bn_bwd_reduce_partial(g, x, (mode, bn.scale, bn.shift))
+                    dgamma, dbeta, c0, c1, _ = _bn_bwd_finish(partial, bn)
+                    p.coef = (mode, c0, c1)
+                p.g = g
+                return None, dgamma, dbeta, dW, dbias, None
             dx, dgamma, dbeta = bn_input_backward(g, x, s.bn_in, s.relu, inplace=True)
             if res is not None:  # (a path whose kernel cannot add it in its store)
                 dx = dx + res
@@ -678,6 +720,8 @@ class _FoldConvFn(torch.autograd.Function):
                     dx = K.bn_bwd_apply(g, x, (PRO_AFFINE, ones, ones), c0, c1, out=g)
                 else:
                     dx = g
+            if s.park is not None and s.park.can_park(GradFork.RAW, dx, x):
+                s.park.g, dx = dx, None  # added by the other consumer's bn_bwd_apply
         return dx, dgamma, dbeta, dW.view_as(weight), None
 
 
@@ -702,6 +746,9 @@ class _DwFn(torch.autograd.Function):
             dy = dy.contiguous()
         dx = dgamma = dbeta = None
         bn = s.bn_in
+        f = s.fork
+        if f is not None:
+            f.closed = True  # (a consumer that runs after this one keeps its gradient)
         tiled = K.dw_tiled(s.stride, s.dil)  # these kernels produce dW in torch's layout, too
         # One pass over (dy, x): masked data gradient + weight-gradient partials + BN sums — every
         # stride-1 layer, and stride 2 / dilation 1 on its own kernel (csrc/dwconv_s2.hip).
@@ -717,15 +764,17 @@ class _DwFn(torch.autograd.Function):
                 g, dW, pb = K.dwconv_bwd_fused_s2(x, dy, weight.detach().contiguous(), s.pro,
                                                   want_bn=bn is not None, raw_dw=raw)
             else:
-                res = None
-                if bn is None and s.fork is not None and s.fork.g is not None \
-                        and K.dwconv_bwd_fused_add_ok(s.dil):
-                    res = s.fork.take()  # the identity path's gradient rides in the store
-                    if res.dtype != x.dtype or tuple(res.shape) != tuple(x.shape):
-                        s.fork.g, res = res, None
+                res, as_sum = None, False
+                if f is not None and f.g is not None and f.kind in (GradFork.POST, GradFork.SUM):
+                    as_sum = f.kind == GradFork.SUM
+                    if bn is None and (K.dwconv_bwd_fused_sum_ok(x.dtype, C, s.dil) if as_sum
+                                       else K.dwconv_bwd_fused_add_ok(s.dil)):
+                        res = s.fork.take()  # the other consumer's gradient rides in the store
+                        if res.dtype != x.dtype or tuple(res.shape) != tuple(x.shape):
+                            s.fork.g, res = res, None
                 g, dW, pb = K.dwconv_bwd_fused(x, dy, _dw_taps(weight, 1, s.dil), s.dil, s.pro,
                                                want_bn=bn is not None, torch_layout=tiled,
-                                               raw_dw=raw, res=res)
+                                               raw_dw=raw, res=res, res_sum=as_sum)
                 if not tiled:
                     dW = K.dw_torch_layout(dW)
             if bn is None:
@@ -736,8 +785,16 @@ class _DwFn(torch.autograd.Function):
                     dW = dWsum
                 if not bn.training:
                     c0 = c1 = None
+                add = add_pro = None
+                if f is not None and f.g is not None and f.kind in (GradFork.RAW, GradFork.PRE) \
+                        and f.g.dtype == g.dtype and tuple(f.g.shape) == tuple(g.shape):
+                    # the other consumer's gradient: w.r.t. the raw tensor, or (PRE) w.r.t. the
+                    # activated one with the coefficients of its own BatchNorm backward
+                    add_pro = f.coef if f.kind == GradFork.PRE else None
+                    add = f.take()
                 # the ReLU mask is already in g: apply only the affine part of the BN backward
-                dx = K.bn_bwd_apply(g, x, (PRO_AFFINE, bn.scale, bn.shift), c0, c1, out=g)
+                dx = K.bn_bwd_apply(g, x, (PRO_AFFINE, bn.scale, bn.shift), c0, c1, out=g, add=add,
+                                    add_pro=add_pro)
         else:
             dW = K.dwconv_wgrad(x, dy, s.stride, s.dil, s.pro, torch_layout=tiled)
             if not tiled:
@@ -746,8 +803,12 @@ class _DwFn(torch.autograd.Function):
                 w = _dw_taps(weight, s.stride, s.dil, reversed=s.stride == 1)
                 g = K.dwconv_dgrad(dy, w, s.stride, s.dil, (x.shape[1], x.shape[2]))
                 dx, dgamma, dbeta = bn_input_backward(g, x, bn, s.relu, inplace=True)
-        if s.fork is not None and s.fork.g is not None and dx is not None:
-            dx = dx + s.fork.take()  # (a path whose kernel cannot add it in its store)
+        if f is not None and f.g is not None and dx is not None:
+            if f.kind == GradFork.PRE:  # (armed only where the fused backward runs: *_fork below)
+                raise RuntimeError("a gradient parked for the depthwise backward's BatchNorm pass "
+                                   "was not taken (stride %d, dilation %d, C %d)"
+                                   % (s.stride, s.dil, C))
+            dx = dx + f.take()  # (a path whose kernel cannot add it in its store)
         return dx, dgamma, dbeta, dW, None
 
 
@@ -792,7 +853,7 @@ class _ApplyFn(torch.autograd.Function):
                                          elem_mul=s.elem_mul)
         dr = dgr = dbr = None
         if ctx.has_r and ctx.needs_input_grad[3]:
-            if s.fork is not None and s.bn_r is None and not s.relu_r:
+            if s.fork is not None and s.bn_r is None and not s.relu_r and not s.fork.closed:
                 s.fork.g = g  # plain identity path: handed to the fork's other consumer
             else:
                 dr, dgr, dbr = bn_input_backward(g, r, s.bn_r, s.relu_r, None, inplace=False)
@@ -1210,6 +1271,9 @@ class _ForkFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n):
+        # an alias nobody differentiates through, or whose consumer handed its gradient to
+        # another one (GradFork), contributes None — not a zero tensor and a pass to add it
+        ctx.set_materialize_grads(False)
         return tuple(x.view(x.shape) for _ in range(n))
 
     @staticmethod
@@ -1420,11 +1484,20 @@ def group_norm(y, gn, out=None):
     return Act(_GroupNormFn.apply(y, gn.weight, gn.bias, gn.num_groups, gn.eps, out))
 
 
-def conv_bn(act, conv, bn=None, out=None, fork=None):
+def _conv_materializes_input(act, conv):
+    """conv_bn writes the activated input of a wide non-folding conv out once (see there)."""
+    return (act.bn is not None or act.relu) and conv.out_channels >= 256
+
+
+def conv_bn(act, conv, bn=None, out=None, fork=None, park=None):
     """conv (nn.Conv2d, groups=1) [+ BatchNorm statistics].  Returns an Act whose BN (if any) and
     ReLU are pending; caller sets ``.relu``.  `fork`: see GradFork (the input is a forked plain
-    activation whose other consumer parks its gradient for this conv's data-gradient GEMM)."""
+    activation whose other consumer parks its gradient for this conv's data-gradient GEMM).
+    `park` (or the input's own `Act.park`): the GradFork this conv parks ITS input gradient in,
+    for the fork's other consumer to add."""
     x = act.t
+    if park is None:
+        park = act.park
     gn = bn if is_group_norm(bn) else None
     if gn is not None:  # the conv keeps its bias and takes no statistics; see _GroupNormFn
         bn = None
@@ -1434,7 +1507,7 @@ def conv_bn(act, conv, bn=None, out=None, fork=None):
     g, b = act.params
     foldable = (act.bn is not None and not act.relu and conv.kernel_size == (1, 1)
                 and conv.padding[0] == 0 and conv.bias is None and not _NO_FOLD)
-    if not foldable and (act.bn is not None or act.relu) and conv.out_channels >= 256:
+    if not foldable and _conv_materializes_input(act, conv):
         # a wide GEMM re-applies the prologue once per 128-column tile of its output
         # (tools/gemm_bench.py: 709 -> 408 TF forward, 419 -> 222 TF weight gradient on
         # 1536->2048): cheaper to materialise the activated tensor once and run plain GEMMs
@@ -1443,6 +1516,8 @@ def conv_bn(act, conv, bn=None, out=None, fork=None):
         spec = ConvSpec(act, conv.stride[0], conv.padding[0], conv.dilation[0], out,
                         want_stats=batch_stats)
         g, b = act.params
+        park = None  # (this conv's input gradient is w.r.t. the materialised copy)
+    spec.park = park
     if foldable:
         spec.drop_const = batch_stats
         y = _FoldConvFn.apply(x, g, b, conv.weight, spec)
@@ -1473,6 +1548,49 @@ def dwconv_bn(act, conv, bn, out=None, fork=None):
         return group_norm(y, gn, out)
     N, Ho, Wo, _ = y.shape
     return Act(y, finish_bn(bn, spec.partial, N * Ho * Wo, y=y))
+
+
+def _bn_backward_is_plain(bn):
+    """Training-mode, single-process BatchNorm off the few-sample path: its backward is reduce ->
+    finalize -> bn_bwd_apply, the chain a parked gradient can join."""
+    return (bn.training and bn.group is None and not isinstance(bn.count, torch.Tensor)
+            and bn.count > K.SMALL_BN_ROWS)
+
+
+def conv_skip_fork(act, conv, dw):
+    """GradFork for a block input `act` read by a shortcut `conv` (conv_bn(park=)) and by the
+    ReLU-first depthwise conv `dw` (dwconv_bn(fork=)), or None where the gradients have to meet
+    in `fork`'s n-ary sum: a plain input whose depthwise backward is not on the sliding kernels,
+    consumers that see different masks, the conv materialises or folds its input, or the pending
+    BatchNorm's backward is not the plain chain (SyncBatchNorm, evaluation mode, few samples)."""
+    t = act.t
+    if not (torch.is_grad_enabled() and t.requires_grad) or t.dim() != 4:
+        return None
+    if dw.stride[0] != 1 or t.shape[-1] % K.vec_of(t.dtype) != 0:
+        return None
+    if act.bn is None and not act.relu:
+        if not K.dwconv_bwd_fused_sum_ok(t.dtype, t.shape[-1], dw.dilation[0]):
+            return None
+        return GradFork(GradFork.SUM)
+    if act.bn is None or not act.relu or _conv_materializes_input(act, conv) \
+            or not _bn_backward_is_plain(act.bn):
+        return None
+    return GradFork(GradFork.PRE)
+
+
+def low_feat_fork(act, dw):
+    """GradFork (RAW) for a deferred activation read by the ReLU-first depthwise conv `dw`
+    (dwconv_bn(fork=)) and, as `Act.park`, by a BN-folding 1x1 conv outside the block — or None
+    where `fork`'s sum has to add the two gradients (conditions as for conv_skip_fork)."""
+    t = act.t
+    if not (torch.is_grad_enabled() and t.requires_grad) or t.dim() != 4:
+        return None
+    C, s, d = t.shape[-1], dw.stride[0], dw.dilation[0]
+    fused = s == 1 or (s == 2 and d == 1 and C % 4 == 0 and dw.weight.dtype == torch.float32)
+    if not fused or C % K.vec_of(t.dtype) != 0 or act.relu or act.bn is None \
+            or not _bn_backward_is_plain(act.bn):
+        return None
+    return GradFork(GradFork.RAW)
 
 
 def materialize(act, residual=None, chan_mul=None, post_relu=False, out=None, elem_mul=None,

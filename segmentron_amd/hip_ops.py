@@ -331,12 +331,20 @@ def dwconv_bwd_fused_add_ok(dil):
     return bool(LIB.query("seg_dwconv3x3_bwd_fused_add_ok", int(dil)))
 
 
+def dwconv_bwd_fused_sum_ok(dtype, C, dil):
+    """Does the fused depthwise backward with a second gradient run on the sliding kernels, which
+    can add it exactly like the separate 2-ary sum (dwconv_bwd_fused(res_sum=True))?"""
+    return bool(LIB.query("seg_dwconv3x3_bwd_fused_sum_ok", _DT[dtype], int(C), int(dil)))
+
+
 def dwconv_bwd_fused(x, dy, w, dil, pro=None, want_bn=False, torch_layout=False, raw_dw=False,
-                     res=None, out=None):
+                     res=None, out=None, res_sum=False):
     """stride-1 depthwise backward in one pass: returns (g masked by the prologue's ReLU,
     dW fp32 [9, C] (or [C,1,3,3] with torch_layout), bn_partial fp32 [gy, 2C] | None).
     w: tap-major [9, C] or (dil <= 2) the [C,1,3,3] parameter itself.
-    out: write g there (an NHWC view, e.g. a channel slice) instead of a fresh tensor."""
+    out: write g there (an NHWC view, e.g. a channel slice) instead of a fresh tensor.
+    res: a second gradient added in the store path, g = mask * dgrad + res — with res_sum the masked
+    gradient is rounded to the storage type first: bit for bit sum_n([g without res, res])."""
     N, H, W, C, ldx = nhwc(x)
     lddy = nhwc(dy)[4]
     mode, ps, pt = _pro(pro)
@@ -347,9 +355,9 @@ def dwconv_bwd_fused(x, dy, w, dil, pro=None, want_bn=False, torch_layout=False,
     pb = torch.empty((gy, 2 * C), dtype=torch.float32, device=x.device) if want_bn else None
     if res is not None:  # g = masked dgrad + res (the other gradient of a forked activation)
         assert dil == 1 and tuple(res.shape) == (N, H, W, C) and res.dtype == x.dtype
-        LIB.call("seg_dwconv3x3_bwd_fused_add", _DT[x.dtype], _p(dy), lddy, _p(x), ldx, N, H, W,
-                 C, _p(w), layout, mode, _p(ps), _p(pt), _p(res), nhwc(res)[4], _p(g), ldg, _p(pw),
-                 _p(pb), gy, _stream())
+        LIB.call("seg_dwconv3x3_bwd_fused_sum" if res_sum else "seg_dwconv3x3_bwd_fused_add",
+                 _DT[x.dtype], _p(dy), lddy, _p(x), ldx, N, H, W, C, _p(w), layout, mode, _p(ps),
+                 _p(pt), _p(res), nhwc(res)[4], _p(g), ldg, _p(pw), _p(pb), gy, _stream())
     else:
         LIB.call("seg_dwconv3x3_bwd_fused", _DT[x.dtype], _p(dy), lddy, _p(x), ldx, N, H, W, C,
                  _p(w), layout, dil, mode, _p(ps), _p(pt), _p(g), ldg, _p(pw), _p(pb), gy, _stream())
@@ -631,13 +639,27 @@ def bn_bwd_finalize(sums, count, mean, invstd, gamma, grad_scale=1.0):
     return out[0], out[1], out[2], out[3]  # dgamma, dbeta, c0, c1
 
 
-def bn_bwd_apply(g, x, pro, c0=None, c1=None, chan_mul=None, out=None, elem_mul=None):
+def bn_bwd_apply(g, x, pro, c0=None, c1=None, chan_mul=None, out=None, elem_mul=None, add=None,
+                 add_pro=None):
+    """add: the gradient another consumer of the same raw tensor parked (the output's shape and
+    dtype), joined in the same pass.  add_pro None: it is w.r.t. the raw tensor and is added as it
+    is; (mode, c0', c1'): it is w.r.t. that consumer's activated input (prologue bits `mode` on
+    the same scale / shift) and takes its own BatchNorm backward with ITS coefficients first.
+    Either way the result is bit for bit sum_n([this apply, that consumer's own dx])."""
     N, H, W, C, ldg = nhwc(g)
     ldx = nhwc(x)[4]
     mode, s, t = _pro(pro)
     if out is None:
         out = torch.empty((N, H, W, C), dtype=g.dtype, device=g.device)
     lddx = nhwc(out)[4]
+    if add is not None:
+        assert chan_mul is None and elem_mul is None
+        assert tuple(add.shape) == (N, H, W, C) and add.dtype == out.dtype
+        am, ac0, ac1 = add_pro if add_pro is not None else (0, None, None)
+        LIB.call("seg_bn_bwd_apply_add", _DT[g.dtype], _p(g), ldg, _p(x), ldx, mode, _p(s), _p(t),
+                 _p(c0), _p(c1), _p(add), nhwc(add)[4], int(am), _p(ac0), _p(ac1), _p(out), lddx,
+                 N * H * W, C, _stream())
+        return out
     ldm = nhwc(elem_mul)[4] if elem_mul is not None else 0
     LIB.call("seg_bn_bwd_apply", _DT[g.dtype], _p(g), ldg, _p(x), ldx, mode, _p(s), _p(t), _p(c0),
              _p(c1), _p(chan_mul), H * W, _p(elem_mul), ldm, _p(out), lddx, N * H * W, C,

@@ -47,19 +47,29 @@ class XceptionBlock(nn.Module):
             fork = F.GradFork()
         skip_in = inputs
         if self.skip_connection_type == "conv":
-            # two consumers (first separable conv, shortcut conv): one 2-ary gradient sum on the
-            # HIP kernel instead of autograd's `add` (functional.fork)
+            # two consumers (first separable conv, shortcut conv): the shortcut conv's backward
+            # parks its data gradient for sep_conv1's depthwise backward, which runs later and
+            # adds it inside its kernel (functional.conv_skip_fork) — where it cannot, the two
+            # gradients meet in one 2-ary sum on the HIP kernel (functional.fork)
+            if self.relu_first:
+                fork = F.conv_skip_fork(inputs, self.conv, self.sep_conv1.block.depthwise)
             t = F.fork(inputs.t, 2)
             inputs, skip_in = F.Act(t[0], inputs.bn, inputs.relu), F.Act(t[1], inputs.bn, inputs.relu)
         sc1 = self.sep_conv1(inputs, fork=fork) if fork is not None else self.sep_conv1(inputs)
         sc2 = self.sep_conv2(sc1)
-        low = sc2
+        low, low_fork = sc2, None
         if self.low_feat:  # the low-level feature leaves the block AND feeds sep_conv3
+            # (its outside consumer, a BN-folding 1x1 conv, parks its gradient for sep_conv3's
+            # depthwise backward: functional.low_feat_fork)
+            if self.relu_first:
+                low_fork = F.low_feat_fork(sc2, self.sep_conv3.block.depthwise)
             t = F.fork(sc2.t, 2)
-            sc2, low = F.Act(t[0], sc2.bn, sc2.relu), F.Act(t[1], sc2.bn, sc2.relu)
-        residual = self.sep_conv3(sc2)
+            sc2 = F.Act(t[0], sc2.bn, sc2.relu)
+            low = F.Act(t[1], sc2.bn, sc2.relu, park=low_fork)
+        residual = self.sep_conv3(sc2, fork=low_fork) if low_fork is not None \
+            else self.sep_conv3(sc2)
         if self.skip_connection_type == "conv":
-            shortcut = F.conv_bn(skip_in, self.conv, self.bn)
+            shortcut = F.conv_bn(skip_in, self.conv, self.bn, park=fork)
             outputs = F.Act(F.materialize(residual, residual=shortcut))
         elif self.skip_connection_type == "sum":
             outputs = F.Act(F.materialize(residual, residual=inputs, fork=fork))
