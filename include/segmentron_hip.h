@@ -404,15 +404,20 @@ int seg_nchw_to_nhwc_pad(int dtype, const float* x, int N, int Cin, int H, int W
  * vector-padded pitch); target: int64 [N, H, W]; loss_out: float32[2] = (mean loss, 1 / number
  * of valid pixels); ws: >= 2 * seg_upsample_ce_blocks(N, H, W) doubles.  Backward: dlo
  * [N, Hi, Wi, lddlo] in `dtype` (channels >= C written as zeros) = grad_out[0] * dLoss/dlo,
- * up-sampling factors up to 16.1 (output-stride-4, -8 and -16 heads).  Deterministic (fixed-order float64 / gather reductions). */
+ * up-sampling factors up to 16.1 (output-stride-4, -8 and -16 heads).  It runs as a row pass and a
+ * column pass around a float32 workspace [N, H, Wi, C] that the caller provides (the entry point
+ * does not allocate): ws of ws_bytes >= seg_upsample_ce_bwd_ws_bytes(N, H, Wi, C) bytes (that
+ * query returns -1 where an int cannot hold the size).  Deterministic (fixed-order float64 /
+ * gather reductions, no atomics). */
 int seg_upsample_ce_blocks(int N, int H, int W);
+int seg_upsample_ce_bwd_ws_bytes(int N, int H, int Wi, int C);
 int seg_upsample_ce_fwd(int dtype, const void* lo, long ld, int N, int Hi, int Wi, int C,
                         const long* target, int H, int W, long ignore_index, int align_corners,
                         double* ws, float* loss_out, void* stream);
 int seg_upsample_ce_bwd(int dtype, const void* lo, long ld, int N, int Hi, int Wi, int C,
                         const long* target, int H, int W, long ignore_index, int align_corners,
                         const float* loss_out, const float* grad_out, void* dlo, long lddlo,
-                        void* stream);
+                        float* ws, long ws_bytes, void* stream);
 
 /* ---- PointRend point head (segmentron/models/pointrend.py:32-195, csrc/pointrend.hip) ---------
  * Maps are addressed through strides: element (n, pixel h*W + w, channel c) at

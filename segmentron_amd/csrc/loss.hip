@@ -6,7 +6,9 @@
 // whose intermediate [N, nclass, H, W] float32 logits (319 MB at 2 x 19 x 1025 x 2049) are
 // written once and read three times by five ATen kernels.  Here they are never
 // materialised: the forward interpolates, soft-maxes and reduces per output pixel; the backward
-// recomputes the soft-max and gathers the gradient straight into the low-resolution tensor.
+// recomputes the soft-max once per output pixel and gathers the gradient into the low-resolution
+// tensor in two separable passes — along w into an fp32 workspace [N, H, Wi, C] (80 MB for the
+// tensor above), then along h.
 //
 // Numerics follow ATen: interpolation in float32 with the tap arithmetic of resize_taps.h and
 // the same association  h0l*(w0l*x00 + w1l*x01) + h1l*(w0l*x10 + w1l*x11); log-softmax as
@@ -172,178 +174,143 @@ __global__ void ce_finalize_kernel(const double* partial, int nblocks, float* ou
   }
 }
 
-// backward: one block per LOW-resolution tile of LT x LT pixels.  The output rows that touch the
-// tile are processed in CHUNKS of CH rows.  Per chunk — phase 1: dz = (softmax - onehot) of the
-// chunk's output pixels (redundantly with the neighbouring tiles at the borders) into LDS;
-// phase 2a: reduced along w with the tile columns' interpolation weights; phase 2b: every
-// (pixel, channel) of the tile adds its weighted rows of the chunk to a register accumulator, in
-// ascending row order — the same fixed summation order as a whole-footprint gather.
-// LT = low-res tile edge, HT_MAX = most output rows / columns that can touch LT low-res rows at
-// up to 4.1x upsampling: (LT + 1.5) * 4.1 + 5.  LDS: NC * CH * (HT_MAX + LT) floats — the first
-// version staged the whole NC x HT_MAX x HT_MAX footprint (137 KiB: ONE 512-thread block per CU,
-// 7396 blocks in 29 rounds of 17 us = 0.5 ms per C3 step, the largest single kernel of the step);
-// with 12-row chunks three blocks share a CU and overlap each other's load / LDS phases.
-constexpr int CE_BWD_THREADS = 512;
-template <typename T, int NC, int LT, int HT_MAX, int CH>
-__global__ __launch_bounds__(CE_BWD_THREADS, 4) void ce_bwd_kernel(const CeArgs a, const float* gscale,
-                                                                   const float* gout, void* dlo,
-                                                                   long lddlo) {
+// backward: the gather  dlo[n][i][j][c] = sum_h wh(h -> i) * sum_w ww(w -> j) * dz[n][h][w][c]  is
+// separable, so it runs as two passes with an fp32 workspace tmp[N][H][Wi][C] between them.
+//   row pass     block = (image, output row h, segment of SJ low-resolution columns).  A thread owns
+//                one output pixel of the segment's footprint: dz = g * (softmax - onehot) into LDS
+//                as [c][w]; then (column j, class c) items reduce along w, ascending over
+//                cand_range(j) with fmaf, and the segment's tmp[n][h][j0 ..][:] — one contiguous run
+//                of the workspace — leaves through LDS as coalesced dword stores.  Only the few
+//                halo pixels a segment shares with its neighbours are computed twice.
+//   column pass  per (n, i, j, c): ascending over cand_range(i) with fmaf from 0, rounded once to
+//                the storage type; channels >= C are written as zero up to the pitch.
+// Every output pixel's softmax is computed once per segment that touches it (the tiled kernel this
+// replaces computed it ~1.27 times at x4 and spent two thirds of its time in three barrier-separated
+// phases per 12-row chunk).  The order of every sum is that of a whole-footprint gather, rows
+// outside columns inside; zero-weight candidates are skipped (fmaf(0, finite, v) == v).  No atomics.
+constexpr int CE_ROW_THREADS = 256;           // the most output pixels a segment's footprint may hold
+constexpr int CE_ROW_PITCH = CE_ROW_THREADS + 1;  // dz row pitch: == 1 (mod 32 banks)
+constexpr int CE_ROW_TPJ = 4;                 // threads that share one column j of the row reduction
+constexpr int CE_ROW_MAX_SJ = 128;            // bounds the LDS of the store staging
+constexpr float CE_MAX_SCALE = 16.1f;         // output-stride-4, -8 and -16 heads
+
+template <typename T, int NC>
+__global__ __launch_bounds__(CE_ROW_THREADS) void ce_bwd_row_kernel(const CeArgs a, const float* gscale,
+                                                                    const float* gout,
+                                                                    float* __restrict__ ws, int SJ) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_ce[];
-  const int tiles_w = (a.Wi + LT - 1) / LT, tiles_h = (a.Hi + LT - 1) / LT;
-  const int tw = blockIdx.x % tiles_w, th = (blockIdx.x / tiles_w) % tiles_h;
-  const int n = blockIdx.x / (tiles_w * tiles_h);
-  const int i0 = th * LT, j0 = tw * LT;
-  const int i1 = min(a.Hi, i0 + LT) - 1, j1 = min(a.Wi, j0 + LT) - 1;
-  // output range touching rows [i0, i1] / columns [j0, j1]
-  int hlo, hhi, wlo, whi, t0, t1;
-  cand_range(a.sh, i0, a.H, a.align, hlo, t1);
-  cand_range(a.sh, i1, a.H, a.align, t0, hhi);
+  float* dz = reinterpret_cast<float*>(smem_ce);     // [C][CE_ROW_PITCH]
+  float* stage = dz + (long)a.C * CE_ROW_PITCH;      // [SJ][C]
+  const int h = blockIdx.y, n = blockIdx.z;
+  const int j0 = blockIdx.x * SJ, j1 = min(a.Wi, j0 + SJ) - 1, nj = j1 - j0 + 1;
+  // output columns touching [j0, j1]: nw <= CE_ROW_THREADS (checked on the host, column by column)
+  int wlo, whi, t0, t1;
   cand_range(a.sw, j0, a.W, a.align, wlo, t1);
   cand_range(a.sw, j1, a.W, a.align, t0, whi);
-  const int nh = hhi - hlo + 1, nw = whi - wlo + 1;  // <= HT_MAX (checked on the host)
-  float* dz = reinterpret_cast<float*>(smem_ce);                  // [NC][CH][HT_MAX]
-  float* tmp = dz + (long)NC * CH * HT_MAX;                       // [NC][CH][LT]
-  float* wth = tmp + (long)NC * CH * LT;                          // [HT_MAX][LT] row weights
-  float* wtw = wth + HT_MAX * LT;                                 // [HT_MAX][LT] column weights
-  int* rng = reinterpret_cast<int*>(wtw + HT_MAX * LT);           // [2][LT][2] candidate ranges
+  const int nw = whi - wlo + 1;
   const float g = gout[0] * gscale[1];  // dLoss * (1 / valid count)
-  // ---- interpolation weights of every (output row, tile row) / (output column, tile column)
-  for (int p = threadIdx.x; p < 2 * HT_MAX * LT; p += CE_BWD_THREADS) {
-    const int which = p / (HT_MAX * LT), q = p - which * HT_MAX * LT;
-    const int oo = q / LT, ii = q - oo * LT;
-    if (which == 0) wth[q] = oo < nh ? tap_weight(a.sh, hlo + oo, a.Hi, a.align, i0 + ii) : 0.f;
-    else wtw[q] = oo < nw ? tap_weight(a.sw, wlo + oo, a.Wi, a.align, j0 + ii) : 0.f;
+  if ((int)threadIdx.x < nw) {
+    const int w = wlo + threadIdx.x;
+    // the target and the four logit taps are requested together (the softmax of an ignored
+    // pixel — 5 % of Cityscapes-like labels — is computed and discarded: a branch on the
+    // target would put a second, dependent memory round trip behind the first)
+    const long t = a.target[((long)n * a.H + h) * a.W + w];
+    float z[NC];
+    ce_logits<T, NC>(a, n, h, w, z);
+    const bool valid = t != a.ignore && t >= 0 && t < a.C;
+    float m = z[0];
+#pragma unroll
+    for (int c = 1; c < NC; ++c) m = (c < a.C) ? fmaxf(m, z[c]) : m;
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      z[c] = (c < a.C) ? expf(z[c] - m) : 0.f;
+      s += z[c];
+    }
+    const float inv = valid ? g / s : 0.f, hot = valid ? g : 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) z[c] = z[c] * inv - (c == (int)t ? hot : 0.f);
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      if (c < a.C) dz[c * CE_ROW_PITCH + threadIdx.x] = z[c];
   }
-  if (threadIdx.x < 2 * LT) {
-    const int which = threadIdx.x / LT, ii = threadIdx.x - which * LT;
+  __syncthreads();
+  // ---- along w: CE_ROW_TPJ threads share a column and split its classes, so a tap weight is
+  // derived once per (column, candidate) and not once per class
+  const int cg = threadIdx.x % CE_ROW_TPJ;
+  for (int jj = threadIdx.x / CE_ROW_TPJ; jj < nj; jj += CE_ROW_THREADS / CE_ROW_TPJ) {
     int clo, chi;
-    if (which == 0) {
-      cand_range(a.sh, i0 + ii, a.H, a.align, clo, chi);
-      clo = max(clo, hlo) - hlo; chi = min(chi, hhi) - hlo;
-    } else {
-      cand_range(a.sw, j0 + ii, a.W, a.align, clo, chi);
-      clo = max(clo, wlo) - wlo; chi = min(chi, whi) - wlo;
+    cand_range(a.sw, j0 + jj, a.W, a.align, clo, chi);
+    float v[NC / CE_ROW_TPJ];
+#pragma unroll
+    for (int k = 0; k < NC / CE_ROW_TPJ; ++k) v[k] = 0.f;
+    for (int w = clo; w <= chi; ++w) {
+      const float wt = tap_weight(a.sw, w, a.Wi, a.align, j0 + jj);
+      if (wt == 0.f) continue;
+      const float* col = dz + (w - wlo);
+#pragma unroll
+      for (int k = 0; k < NC / CE_ROW_TPJ; ++k) {
+        const int c = cg + k * CE_ROW_TPJ;
+        if (c < a.C) v[k] = fmaf(wt, col[c * CE_ROW_PITCH], v[k]);
+      }
     }
-    rng[(which * LT + ii) * 2] = clo;
-    rng[(which * LT + ii) * 2 + 1] = chi;
+#pragma unroll
+    for (int k = 0; k < NC / CE_ROW_TPJ; ++k) {
+      const int c = cg + k * CE_ROW_TPJ;
+      if (c < a.C) stage[jj * a.C + c] = v[k];
+    }
   }
-  const int lw_n = j1 - j0 + 1, lh_n = i1 - i0 + 1;
-  // this thread's (tile pixel, channel) items of phase 2b: p = (ii * LT + jj) * lddlo + c
-  constexpr int MAXI = (LT * LT * 32 + CE_BWD_THREADS - 1) / CE_BWD_THREADS;
-  const int ld = (int)lddlo, nitems = LT * LT * ld;
-  float acc[MAXI];
-#pragma unroll
-  for (int k = 0; k < MAXI; ++k) acc[k] = 0.f;
+  __syncthreads();
+  float* __restrict__ out = ws + (((long)n * a.H + h) * a.Wi + j0) * a.C;
+  for (int p = threadIdx.x; p < nj * a.C; p += CE_ROW_THREADS) out[p] = stage[p];
+}
 
-  for (int r0 = 0; r0 < nh; r0 += CH) {
-    const int rows = min(CH, nh - r0);
-    // ---- phase 1: the chunk's output pixels (at most one per thread: rows * nw <= 432)
-#pragma unroll 1
-    for (int p = threadIdx.x; p < rows * nw; p += CE_BWD_THREADS) {
-      const int hh = p / nw, ww = p - hh * nw;
-      const int h = hlo + r0 + hh, w = wlo + ww;
-      // the target and the four logit taps are requested together (the softmax of an ignored
-      // pixel — 5 % of Cityscapes-like labels — is computed and discarded: a branch on the
-      // target would put a second, dependent memory round trip behind the first)
-      const long t = a.target[((long)n * a.H + h) * a.W + w];
-      float z[NC];
-      ce_logits<T, NC>(a, n, h, w, z);
-      const bool valid = t != a.ignore && t >= 0 && t < a.C;
-      float m = z[0];
-#pragma unroll
-      for (int c = 1; c < NC; ++c) m = (c < a.C) ? fmaxf(m, z[c]) : m;
-      float s = 0.f;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        z[c] = (c < a.C) ? expf(z[c] - m) : 0.f;
-        s += z[c];
-      }
-      const float inv = valid ? g / s : 0.f, hot = valid ? g : 0.f;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) z[c] = z[c] * inv - (c == (int)t ? hot : 0.f);
-#pragma unroll
-      for (int c = 0; c < NC; ++c) dz[((long)c * CH + hh) * HT_MAX + ww] = z[c];
-    }
-    __syncthreads();  // (also orders the weight tables / the previous chunk's phase 2b)
-    // ---- phase 2a: along w.  tmp[c][hh][jj] = sum_ww wtw[ww][jj] * dz[c][hh][ww]
-    for (int p = threadIdx.x; p < a.C * rows * LT; p += CE_BWD_THREADS) {
-      const int jj = p % LT, hh = (p / LT) % rows, c = p / (LT * rows);
-      float v = 0.f;
-      if (jj < lw_n) {
-        const int clo = rng[(LT + jj) * 2], chi = rng[(LT + jj) * 2 + 1];
-        const float* row = dz + ((long)c * CH + hh) * HT_MAX;
-        for (int ww = clo; ww <= chi; ++ww) v = fmaf(wtw[ww * LT + jj], row[ww], v);
-      }
-      tmp[((long)c * CH + hh) * LT + jj] = v;
+constexpr int CE_COL_THREADS = 256;
+constexpr int CE_COL_BATCH = 8;  // workspace rows requested together
+template <typename T>
+__global__ __launch_bounds__(CE_COL_THREADS) void ce_bwd_col_kernel(const float* __restrict__ ws,
+                                                                    T* __restrict__ dlo, int ld,
+                                                                    int Hi, int Wi, int H, int C,
+                                                                    float sh, int align) {
+  // the rows of cand_range(i) that carry weight, ascending, 64 candidates at a time
+  __shared__ float s_wt[64];
+  __shared__ int s_row[64];
+  __shared__ int s_cnt;
+  const int i = blockIdx.y, n = blockIdx.z;
+  const int q = blockIdx.x * CE_COL_THREADS + threadIdx.x;  // (j, c) of the padded row
+  const int j = q / ld, c = q - j * ld;
+  const bool live = j < Wi && c < C;
+  const float* __restrict__ src = ws + ((long)n * H * Wi + (live ? j : 0)) * C + (live ? c : 0);
+  const long pitch = (long)Wi * C;
+  int hlo, hhi;
+  cand_range(sh, i, H, align, hlo, hhi);
+  float acc = 0.f;
+  for (int hb = hlo; hb <= hhi; hb += 64) {
+    if (threadIdx.x < 64) {
+      const int h = hb + threadIdx.x;
+      const float wt = h <= hhi ? tap_weight(sh, h, Hi, align, i) : 0.f;
+      const unsigned long long mask = __ballot(wt != 0.f);
+      const int pos = __popcll(mask & ((1ull << threadIdx.x) - 1ull));
+      if (wt != 0.f) { s_wt[pos] = wt; s_row[pos] = h; }
+      if (threadIdx.x == 0) s_cnt = __popcll(mask);
     }
     __syncthreads();
-    // ---- phase 2b: along h, this chunk's rows (ascending: the whole sum runs in row order)
+    const int cnt = s_cnt;
+    if (live) {
+      // CE_COL_BATCH loads in flight at a time (slots past the end of the list repeat its last
+      // load and are not added)
+      for (int k0 = 0; k0 < cnt; k0 += CE_COL_BATCH) {
+        float v[CE_COL_BATCH];
 #pragma unroll
-    for (int k = 0; k < MAXI; ++k) {
-      const int p = threadIdx.x + k * CE_BWD_THREADS;
-      if (p < nitems) {
-        const int c = p % ld, jj = (p / ld) % LT, ii = p / (ld * LT);
-        if (c < a.C && ii < lh_n && jj < lw_n) {
-          const int clo = max(rng[ii * 2], r0), chi = min(rng[ii * 2 + 1], r0 + rows - 1);
-          float v = acc[k];
-          for (int hh = clo; hh <= chi; ++hh)
-            v = fmaf(wth[hh * LT + ii], tmp[((long)c * CH + (hh - r0)) * LT + jj], v);
-          acc[k] = v;
-        }
+        for (int u = 0; u < CE_COL_BATCH; ++u) v[u] = src[s_row[min(k0 + u, cnt - 1)] * pitch];
+#pragma unroll
+        for (int u = 0; u < CE_COL_BATCH; ++u)
+          if (k0 + u < cnt) acc = fmaf(s_wt[k0 + u], v[u], acc);
       }
     }
+    __syncthreads();
   }
-  // ---- store (channels >= C are written as zero padding)
-  T* __restrict__ D = reinterpret_cast<T*>(dlo);
-#pragma unroll
-  for (int k = 0; k < MAXI; ++k) {
-    const int p = threadIdx.x + k * CE_BWD_THREADS;
-    if (p < nitems) {
-      const int c = p % ld, jj = (p / ld) % LT, ii = p / (ld * LT);
-      if (ii < lh_n && jj < lw_n)
-        Vec<T>::store1(D + (((long)n * a.Hi + i0 + ii) * a.Wi + j0 + jj) * lddlo + c, acc[k]);
-    }
-  }
-}
-
-template <int NC, int LT, int HT_MAX, int CH> constexpr size_t ce_bwd_lds() {
-  return ((size_t)NC * CH * HT_MAX + (size_t)NC * CH * LT + 2 * (size_t)HT_MAX * LT) *
-             sizeof(float) + 4 * (size_t)LT * sizeof(int);
-}
-// <= 24 classes: 6 x 6 tiles, 12-row chunks (49 KiB of LDS); <= 32 classes: 4 x 4 tiles, 10-row
-// chunks (41 KiB): three blocks per CU
-constexpr int CE_LT24 = 6, CE_HT24 = 36, CE_CH24 = 12, CE_LT32 = 4, CE_HT32 = 28, CE_CH32 = 10;
-static_assert(ce_bwd_lds<24, CE_LT24, CE_HT24, CE_CH24>() <= 53 * 1024, "LDS budget (3 blocks/CU)");
-static_assert(ce_bwd_lds<32, CE_LT32, CE_HT32, CE_CH32>() <= 53 * 1024, "LDS budget (3 blocks/CU)");
-// r05: up to 8.1x (output-stride-8 heads: PSPNet / DANet / CCNet logits at 129x257 for a 1025x2049
-// image; the PSPNet train step paid 6.5 ms of 72 for materialised logits + torch's log-softmax /
-// NLL kernels): the same kernel on 3 x 3 (2 x 2) low-resolution tiles, (LT + 1.5) * 8.1 + 5 rows
-constexpr int CE8_LT24 = 3, CE8_HT24 = 42, CE8_LT32 = 2, CE8_HT32 = 34;
-static_assert(ce_bwd_lds<24, CE8_LT24, CE8_HT24, CE_CH24>() <= 53 * 1024, "LDS budget (3 blocks/CU)");
-static_assert(ce_bwd_lds<32, CE8_LT32, CE8_HT32, CE_CH32>() <= 53 * 1024, "LDS budget (3 blocks/CU)");
-constexpr float CE_MAX_SCALE = 4.1f, CE8_MAX_SCALE = 8.1f;
-static_assert((CE_LT24 + 1.5f) * CE_MAX_SCALE + 5 <= CE_HT24 + 1 && (CE_LT32 + 1.5f) * CE_MAX_SCALE + 5 <= CE_HT32 + 1, "");
-static_assert((CE8_LT24 + 1.5f) * CE8_MAX_SCALE + 5 <= CE8_HT24 && (CE8_LT32 + 1.5f) * CE8_MAX_SCALE + 5 <= CE8_HT32, "");
-// up to 16.1x (output-stride-16 logits resized to the crop: PointRend's coarse-logit loss,
-// segmentron/solver/loss.py:374): 2 x 2 low-resolution tiles, (2 + 1.5) * 16.1 + 5 = 61.4 rows; the
-// chunk shrinks to 8 (6) rows so that three blocks still share a CU
-constexpr int CE16_LT = 2, CE16_HT = 62, CE16_CH24 = 8, CE16_CH32 = 6;
-constexpr float CE16_MAX_SCALE = 16.1f;
-static_assert(ce_bwd_lds<24, CE16_LT, CE16_HT, CE16_CH24>() <= 53 * 1024, "LDS budget (3 blocks/CU)");
-static_assert(ce_bwd_lds<32, CE16_LT, CE16_HT, CE16_CH32>() <= 53 * 1024, "LDS budget (3 blocks/CU)");
-static_assert((CE16_LT + 1.5f) * CE16_MAX_SCALE + 5 <= CE16_HT, "");
-
-template <typename T, int NC, int LT, int HT, int CH>
-static int launch_ce_bwd(int blocks, hipStream_t st, const CeArgs& a, const float* loss_out,
-                         const float* grad_out, void* dlo, long lddlo) {
-  constexpr size_t lds = ce_bwd_lds<NC, LT, HT, CH>();
-  static const int once = (int)hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&ce_bwd_kernel<T, NC, LT, HT, CH>),
-      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  SEG_REQUIRE(once == 0, "upsample_ce_bwd: cannot reserve %d bytes of LDS", (int)lds);
-  hipLaunchKernelGGL((ce_bwd_kernel<T, NC, LT, HT, CH>), dim3(blocks), dim3(CE_BWD_THREADS), lds, st,
-                     a, loss_out, grad_out, dlo, lddlo);
-  return 0;
+  if (j < Wi) Vec<T>::store1(dlo + (((long)n * Hi + i) * Wi + j) * ld + c, acc);
 }
 
 }  // namespace seg
@@ -383,57 +350,83 @@ extern "C" int seg_upsample_ce_fwd(int dtype, const void* lo, long ld, int N, in
   return check_launch("upsample_ce_fwd");
 }
 
+// Segment width of the row pass: the most low-resolution columns whose footprint of output columns,
+// (SJ + 1.5) / scale + 5 at the outside, still fits one block, spread evenly over the segments
+static int ce_bwd_seg_width(int Wi, float sw) {
+  int sj = 1;
+  if (sw > 0.f) {
+    sj = (int)floorf((float)(seg::CE_ROW_THREADS - 5) * sw - 1.5f);
+    sj = sj < 1 ? 1 : (sj > seg::CE_ROW_MAX_SJ ? seg::CE_ROW_MAX_SJ : sj);
+  }
+  const int nseg = (Wi + sj - 1) / sj;
+  return (Wi + nseg - 1) / nseg;
+}
+
+// bytes of the fp32 workspace [N][H][Wi][C] between the two passes of seg_upsample_ce_bwd
+// (-1: more than an int holds)
+extern "C" int seg_upsample_ce_bwd_ws_bytes(int N, int H, int Wi, int C) {
+  if (N <= 0 || H <= 0 || Wi <= 0 || C <= 0) return 0;
+  const long b = (long)N * H * Wi * C * (long)sizeof(float);
+  return b > 0x7fffffffL ? -1 : (int)b;
+}
+
 extern "C" int seg_upsample_ce_bwd(int dtype, const void* lo, long ld, int N, int Hi, int Wi, int C,
                                    const long* target, int H, int W, long ignore_index,
                                    int align_corners, const float* loss_out, const float* grad_out,
-                                   void* dlo, long lddlo, void* stream) {
+                                   void* dlo, long lddlo, float* ws, long ws_bytes, void* stream) {
   using namespace seg;
   SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "upsample_ce_bwd: bad dtype %d", dtype);
   const int vec = dtype == DT_BF16 ? 8 : 4;
-  // the per-thread accumulators of ce_bwd_kernel cover LT*LT*32 items: a wider pitch would leave
-  // part of the gradient tile unwritten
   SEG_REQUIRE(C >= 1 && C <= 32 && ld % vec == 0 && lddlo >= C && lddlo <= 32,
               "upsample_ce_bwd: bad C / pitch (1 <= C <= lddlo <= 32)");
+  SEG_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && H > 0 && W > 0, "upsample_ce_bwd: empty problem");
   SEG_REQUIRE(H >= Hi && W >= Wi, "upsample_ce_bwd: the fused loss is for UP-sampling heads");
-  // a low-res tile row is touched by at most HT_MAX output rows / columns up to 4.1x (8.1x, 16.1x)
   const float sh = host_scale(Hi, H, align_corners), sw = host_scale(Wi, W, align_corners);
   const float smin = fminf(sh > 0.f ? sh : 1.f, sw > 0.f ? sw : 1.f);
-  SEG_REQUIRE(1.f / smin <= CE16_MAX_SCALE,
+  SEG_REQUIRE(1.f / smin <= CE_MAX_SCALE,
               "upsample_ce_bwd: scale factor %.2f too large for the fused backward", 1.f / smin);
+  SEG_REQUIRE(N <= 65535 && H <= 65535, "upsample_ce_bwd: N=%d / H=%d beyond the launch grid", N, H);
+  SEG_REQUIRE(ws && ws_bytes >= (long)N * H * Wi * C * (long)sizeof(float),
+              "upsample_ce_bwd: workspace of %ld bytes, seg_upsample_ce_bwd_ws_bytes asks for more",
+              ws_bytes);
+  // every column's candidate range must lie inside the footprint of the segment that owns it, and
+  // the footprint inside the block: the kernel's own float formulas, column by column
+  const int SJ = ce_bwd_seg_width(Wi, sw), nseg = (Wi + SJ - 1) / SJ;
+  for (int s = 0; s < nseg; ++s) {
+    const int j0 = s * SJ, j1 = (j0 + SJ < Wi ? j0 + SJ : Wi) - 1;
+    int wlo, whi, t0, t1;
+    cand_range(sw, j0, W, align_corners, wlo, t1);
+    cand_range(sw, j1, W, align_corners, t0, whi);
+    SEG_REQUIRE(whi - wlo + 1 <= CE_ROW_THREADS,
+                "upsample_ce_bwd: columns %d..%d touch %d output columns, a block holds %d", j0, j1,
+                whi - wlo + 1, CE_ROW_THREADS);
+    for (int j = j0; j <= j1; ++j) {
+      int clo, chi;
+      cand_range(sw, j, W, align_corners, clo, chi);
+      SEG_REQUIRE(clo >= wlo && chi <= whi && clo <= chi,
+                  "upsample_ce_bwd: column %d gathers outside its segment", j);
+    }
+  }
   CeArgs a;
   a.lo = lo; a.target = target; a.ld = ld; a.N = N; a.Hi = Hi; a.Wi = Wi; a.H = H; a.W = W;
   a.C = C; a.ignore = ignore_index; a.align = align_corners; a.sh = sh; a.sw = sw;
   hipStream_t st = (hipStream_t)stream;
   const int nc = C <= 24 ? 24 : 32;
-  if (1.f / smin > CE8_MAX_SCALE) {  // 8.1x .. 16.1x: the 2 x 2 tile instances
-    const int blocks16 = N * ((Hi + CE16_LT - 1) / CE16_LT) * ((Wi + CE16_LT - 1) / CE16_LT);
-    int rc16;
-    if (dtype == DT_BF16)
-      rc16 = nc == 24 ? launch_ce_bwd<bf16_t, 24, CE16_LT, CE16_HT, CE16_CH24>(blocks16, st, a, loss_out, grad_out, dlo, lddlo)
-                      : launch_ce_bwd<bf16_t, 32, CE16_LT, CE16_HT, CE16_CH32>(blocks16, st, a, loss_out, grad_out, dlo, lddlo);
-    else
-      rc16 = nc == 24 ? launch_ce_bwd<float, 24, CE16_LT, CE16_HT, CE16_CH24>(blocks16, st, a, loss_out, grad_out, dlo, lddlo)
-                      : launch_ce_bwd<float, 32, CE16_LT, CE16_HT, CE16_CH32>(blocks16, st, a, loss_out, grad_out, dlo, lddlo);
-    if (rc16) return rc16;
-    return check_launch("upsample_ce_bwd");
-  }
-  const bool wide = 1.f / smin > CE_MAX_SCALE;  // 4.1x .. 8.1x: the small-tile instances
-  const int lt = wide ? (nc == 24 ? CE8_LT24 : CE8_LT32) : (nc == 24 ? CE_LT24 : CE_LT32);
-  const int blocks = N * ((Hi + lt - 1) / lt) * ((Wi + lt - 1) / lt);
-  int rc;
-  if (wide && dtype == DT_BF16) {
-    rc = nc == 24 ? launch_ce_bwd<bf16_t, 24, CE8_LT24, CE8_HT24, CE_CH24>(blocks, st, a, loss_out, grad_out, dlo, lddlo)
-                  : launch_ce_bwd<bf16_t, 32, CE8_LT32, CE8_HT32, CE_CH32>(blocks, st, a, loss_out, grad_out, dlo, lddlo);
-  } else if (wide) {
-    rc = nc == 24 ? launch_ce_bwd<float, 24, CE8_LT24, CE8_HT24, CE_CH24>(blocks, st, a, loss_out, grad_out, dlo, lddlo)
-                  : launch_ce_bwd<float, 32, CE8_LT32, CE8_HT32, CE_CH32>(blocks, st, a, loss_out, grad_out, dlo, lddlo);
-  } else if (dtype == DT_BF16) {
-    rc = nc == 24 ? launch_ce_bwd<bf16_t, 24, CE_LT24, CE_HT24, CE_CH24>(blocks, st, a, loss_out, grad_out, dlo, lddlo)
-                  : launch_ce_bwd<bf16_t, 32, CE_LT32, CE_HT32, CE_CH32>(blocks, st, a, loss_out, grad_out, dlo, lddlo);
+  const size_t lds = ((size_t)C * CE_ROW_PITCH + (size_t)SJ * C) * sizeof(float);  // <= 49 KiB
+  const dim3 rgrid(nseg, H, N);
+  if (dtype == DT_BF16) {
+    if (nc == 24) hipLaunchKernelGGL((ce_bwd_row_kernel<bf16_t, 24>), rgrid, dim3(CE_ROW_THREADS), lds, st, a, loss_out, grad_out, ws, SJ);
+    else hipLaunchKernelGGL((ce_bwd_row_kernel<bf16_t, 32>), rgrid, dim3(CE_ROW_THREADS), lds, st, a, loss_out, grad_out, ws, SJ);
   } else {
-    rc = nc == 24 ? launch_ce_bwd<float, 24, CE_LT24, CE_HT24, CE_CH24>(blocks, st, a, loss_out, grad_out, dlo, lddlo)
-                  : launch_ce_bwd<float, 32, CE_LT32, CE_HT32, CE_CH32>(blocks, st, a, loss_out, grad_out, dlo, lddlo);
+    if (nc == 24) hipLaunchKernelGGL((ce_bwd_row_kernel<float, 24>), rgrid, dim3(CE_ROW_THREADS), lds, st, a, loss_out, grad_out, ws, SJ);
+    else hipLaunchKernelGGL((ce_bwd_row_kernel<float, 32>), rgrid, dim3(CE_ROW_THREADS), lds, st, a, loss_out, grad_out, ws, SJ);
   }
-  if (rc) return rc;
+  const dim3 cgrid((unsigned)(((long)Wi * lddlo + CE_COL_THREADS - 1) / CE_COL_THREADS), Hi, N);
+  if (dtype == DT_BF16)
+    hipLaunchKernelGGL((ce_bwd_col_kernel<bf16_t>), cgrid, dim3(CE_COL_THREADS), 0, st, ws,
+                       reinterpret_cast<bf16_t*>(dlo), (int)lddlo, Hi, Wi, H, C, sh, align_corners);
+  else
+    hipLaunchKernelGGL((ce_bwd_col_kernel<float>), cgrid, dim3(CE_COL_THREADS), 0, st, ws,
+                       reinterpret_cast<float*>(dlo), (int)lddlo, Hi, Wi, H, C, sh, align_corners);
   return check_launch("upsample_ce_bwd");
 }

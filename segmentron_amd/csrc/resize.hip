@@ -6,8 +6,10 @@
 // arithmetic as ATen's upsample_bilinear2d: scale = (in-1)/(out-1), src = scale*dst,
 // i0 = floor(src), i1 = min(i0+1, in-1), lambda = src - i0).
 // Backward is written as a GATHER over the forward's own tap computation (no atomics, bitwise
-// deterministic): an input pixel scans the small window of outputs that can reference it and
-// re-derives their (i0, i1, lambda).
+// deterministic): an input pixel collects from the small window of outputs that can reference it,
+// whose (i0, i1, lambda) are re-derived — once per block, as lists of the rows and columns that
+// carry weight.  Forward and backward blocks own one row of pixels (block-uniform row taps, no
+// division per element); the forward applies the pending BatchNorm / ReLU once per source vector.
 #include "common.h"
 #include "resize_taps.h"
 
@@ -24,33 +26,75 @@ struct ResizeArgs {
   float sh, sw;
 };
 
+// forward: block = (image, output row, segment of output columns, block of <= RSF_CVB channel
+// vectors).  The row's taps are block-uniform.  The two source rows of the segment are staged ONCE,
+// after the pending BatchNorm / ReLU prologue, as unrounded fp32 in LDS (one thread per source
+// vector used to apply the prologue to each of its four taps: four times the activation work at x4),
+// then threads = (channel vector, column) blend from LDS with the same expression and association.
+// No division per element: the indices come from the block and two small per-thread quotients.
+constexpr int RSF_CVB = 32;             // channel vectors per block: 512 contiguous bytes per pixel
+constexpr int RSF_LDS_FLOATS = 8192;    // 32 KiB of staged source: five blocks share a CU
+constexpr int RSF_MAX_SEG = 256;        // output columns per segment, at the most
+
 template <typename T>
-__global__ __launch_bounds__(RS_THREADS) void bilinear_fwd_kernel(const ResizeArgs a) {
-  constexpr int VEC = Vec<T>::N;
+__global__ __launch_bounds__(RS_THREADS) void bilinear_fwd_kernel(const ResizeArgs a, int segw,
+                                                                  int nseg, int ns_cap, int cvb) {
+  constexpr int VEC = Vec<T>::N, Q = VEC / 4;
+  extern __shared__ float4 rs_stage[];  // [2 rows][ns_cap source columns][Q][cvb] float4
   const T* __restrict__ X = reinterpret_cast<const T*>(a.x);
   T* __restrict__ Y = reinterpret_cast<T*>(a.y);
-  const long total = (long)a.N * a.Ho * a.Wo * a.CV;
-  for (long i = (long)blockIdx.x * RS_THREADS + threadIdx.x; i < total;
-       i += (long)gridDim.x * RS_THREADS) {
-    const int cv = (int)(i % a.CV);
-    long p = i / a.CV;
-    const int wo = (int)(p % a.Wo); p /= a.Wo;
-    const int ho = (int)(p % a.Ho);
-    const int n = (int)(p / a.Ho);
-    const int c0 = cv * VEC;
-    int h0, h1, w0, w1; float lh, lw;
-    taps(a.sh, ho, a.Hi, a.align, h0, h1, lh);
-    taps(a.sw, wo, a.Wi, a.align, w0, w1, lw);
-    const long base = (long)n * a.Hi * a.Wi;
+  const int seg = blockIdx.x % nseg, cv0 = (blockIdx.x / nseg) * cvb;
+  const int ho = blockIdx.y, n = blockIdx.z;
+  const int ncv = min(cvb, a.CV - cv0);
+  const int wo0 = seg * segw, ncol = min(a.Wo, wo0 + segw) - wo0;
+  int h0, h1, s0, s1, t0, t1; float lh, tl;
+  taps(a.sh, ho, a.Hi, a.align, h0, h1, lh);
+  taps(a.sw, wo0, a.Wi, a.align, s0, t1, tl);
+  taps(a.sw, wo0 + ncol - 1, a.Wi, a.align, t0, s1, tl);
+  const int ns = s1 - s0 + 1;  // source columns the segment touches: <= ns_cap (checked on the host)
+  const long base = (long)n * a.Hi * a.Wi;
+  const int step_p = RS_THREADS / ncv, step_c = RS_THREADS - step_p * ncv;
+  int pix = threadIdx.x / ncv, cvl = threadIdx.x - pix * ncv;  // item = (row, source column) x vector
+  const int my_col = pix, my_cvl = cvl;
+  while (pix < 2 * ns) {
+    const int r = pix >= ns ? 1 : 0, s = pix - r * ns;
+    const int c0 = (cv0 + cvl) * VEC;
+    float f[VEC];
+    Vec<T>::unpack(ldg16(X + (base + (long)(r ? h1 : h0) * a.Wi + s0 + s) * a.ldx + c0), f);
+    apply_prologue<VEC>(f, a.mode, a.scale, a.shift, c0);
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+      rs_stage[((r * ns_cap + s) * Q + q) * cvb + cvl] =
+          make_float4(f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]);
+    pix += step_p; cvl += step_c;
+    if (cvl >= ncv) { cvl -= ncv; ++pix; }
+  }
+  __syncthreads();
+  if (my_col >= step_p) return;  // RS_THREADS is no multiple of ncv: the last few threads
+  const int c0 = (cv0 + my_cvl) * VEC;
+  float mul[VEC];
+  if (a.chan_mul) {
+    const float* m = a.chan_mul + (long)n * a.C + c0;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) mul[k] = m[k];
+  }
+  T* __restrict__ yrow = Y + (((long)n * a.Ho + ho) * a.Wo + wo0) * a.ldy + c0;
+  for (int col = my_col; col < ncol; col += step_p) {
+    int w0, w1; float lw;
+    taps(a.sw, wo0 + col, a.Wi, a.align, w0, w1, lw);
+    const float4* p00 = rs_stage + (long)(w0 - s0) * Q * cvb + my_cvl;
+    const float4* p01 = rs_stage + (long)(w1 - s0) * Q * cvb + my_cvl;
+    const float4* p10 = p00 + (long)ns_cap * Q * cvb;
+    const float4* p11 = p01 + (long)ns_cap * Q * cvb;
     float f00[VEC], f01[VEC], f10[VEC], f11[VEC];
-    Vec<T>::unpack(ldg16(X + (base + (long)h0 * a.Wi + w0) * a.ldx + c0), f00);
-    Vec<T>::unpack(ldg16(X + (base + (long)h0 * a.Wi + w1) * a.ldx + c0), f01);
-    Vec<T>::unpack(ldg16(X + (base + (long)h1 * a.Wi + w0) * a.ldx + c0), f10);
-    Vec<T>::unpack(ldg16(X + (base + (long)h1 * a.Wi + w1) * a.ldx + c0), f11);
-    apply_prologue<VEC>(f00, a.mode, a.scale, a.shift, c0);
-    apply_prologue<VEC>(f01, a.mode, a.scale, a.shift, c0);
-    apply_prologue<VEC>(f10, a.mode, a.scale, a.shift, c0);
-    apply_prologue<VEC>(f11, a.mode, a.scale, a.shift, c0);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const float4 v00 = p00[q * cvb], v01 = p01[q * cvb], v10 = p10[q * cvb], v11 = p11[q * cvb];
+      f00[4 * q] = v00.x; f00[4 * q + 1] = v00.y; f00[4 * q + 2] = v00.z; f00[4 * q + 3] = v00.w;
+      f01[4 * q] = v01.x; f01[4 * q + 1] = v01.y; f01[4 * q + 2] = v01.z; f01[4 * q + 3] = v01.w;
+      f10[4 * q] = v10.x; f10[4 * q + 1] = v10.y; f10[4 * q + 2] = v10.z; f10[4 * q + 3] = v10.w;
+      f11[4 * q] = v11.x; f11[4 * q + 1] = v11.y; f11[4 * q + 2] = v11.z; f11[4 * q + 3] = v11.w;
+    }
     float o[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
@@ -59,50 +103,117 @@ __global__ __launch_bounds__(RS_THREADS) void bilinear_fwd_kernel(const ResizeAr
       o[k] = (1.f - lh) * top + lh * bot;
     }
     if (a.chan_mul) {
-      const float* m = a.chan_mul + (long)n * a.C + c0;
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) o[k] *= m[k];
+      for (int k = 0; k < VEC; ++k) o[k] *= mul[k];
     }
-    stg16(Y + (((long)n * a.Ho + ho) * a.Wo + wo) * a.ldy + c0, Vec<T>::pack(o));
+    stg16(yrow + (long)col * a.ldy, Vec<T>::pack(o));
   }
 }
 
-// gx[n,hi,wi,:] = sum over outputs of weight * gy  (x side: Hi x Wi, y side: Ho x Wo)
+// gx[n,hi,wi,:] = sum over outputs of weight * gy  (x side: Hi x Wi, y side: Ho x Wo).
+// Block = (image, source row, segment of source columns, block of channel vectors); a thread owns
+// one source vector.  The rows of cand_range(hi) that carry weight and, per source column, the
+// output columns that carry weight are listed ONCE per block in LDS with their weights (one thread
+// per source vector used to re-derive tap_weight() for all 11 x 11 candidates of a x4 upsample, of
+// which 7 x 7 carry weight, behind three 64-bit divisions).  The gather then runs over the two
+// lists in the same order as before — ho ascending, wo ascending, acc = fmaf(wh * ww, g, acc) —
+// with RSB_BATCH independent loads in flight; neighbouring source columns of a block read
+// the same gradient rows at the same time.  Column lists that do not fit the table (use_tab == 0:
+// magnifications far beyond any model here) are derived on the fly instead.
+constexpr int RSB_TAB = 2048;  // (weight, column) entries of the column lists: 16 KiB
+constexpr int RSB_BATCH = 8;   // gradient vectors requested together
 template <typename T>
-__global__ __launch_bounds__(RS_THREADS) void bilinear_bwd_kernel(const ResizeArgs a) {
+__global__ __launch_bounds__(RS_THREADS) void bilinear_bwd_kernel(const ResizeArgs a, int nsc,
+                                                                  int nsegs, int kc, int cvb,
+                                                                  int use_tab) {
   constexpr int VEC = Vec<T>::N;
+  __shared__ float s_cw[RSB_TAB];
+  __shared__ int s_co[RSB_TAB];
+  __shared__ float s_rw[64];
+  __shared__ int s_ro[64];
+  __shared__ int s_rn;
   const T* __restrict__ GY = reinterpret_cast<const T*>(a.y);
   T* __restrict__ GX = reinterpret_cast<T*>(const_cast<void*>(a.x));
-  const long total = (long)a.N * a.Hi * a.Wi * a.CV;
-  for (long i = (long)blockIdx.x * RS_THREADS + threadIdx.x; i < total;
-       i += (long)gridDim.x * RS_THREADS) {
-    const int cv = (int)(i % a.CV);
-    long p = i / a.CV;
-    const int wi = (int)(p % a.Wi); p /= a.Wi;
-    const int hi = (int)(p % a.Hi);
-    const int n = (int)(p / a.Hi);
-    const int c0 = cv * VEC;
-    int hlo, hhi, wlo, whi;
-    cand_range(a.sh, hi, a.Ho, a.align, hlo, hhi);
-    cand_range(a.sw, wi, a.Wo, a.align, wlo, whi);
-    float acc[VEC];
+  const int seg = blockIdx.x % nsegs, cv0 = (blockIdx.x / nsegs) * cvb;
+  const int hi = blockIdx.y, n = blockIdx.z;
+  const int ncv = min(cvb, a.CV - cv0);
+  const int sc = threadIdx.x / ncv, cvl = threadIdx.x - sc * ncv;
+  const int wi = seg * nsc + sc;
+  const bool live = sc < nsc && wi < a.Wi;
+  const int c0 = (cv0 + cvl) * VEC;
+  int hlo, hhi, wlo = 0, whi = -1, cn = 0;
+  cand_range(a.sh, hi, a.Ho, a.align, hlo, hhi);
+  if (live) cand_range(a.sw, wi, a.Wo, a.align, wlo, whi);
+  if (use_tab && live && cvl == 0) {
+    for (int wo = wlo; wo <= whi; ++wo) {
+      const float ww = tap_weight(a.sw, wo, a.Wi, a.align, wi);
+      if (ww == 0.f) continue;
+      s_cw[sc * kc + cn] = ww;
+      s_co[sc * kc + cn] = wo;
+      ++cn;
+    }
+    s_cw[sc * kc + kc - 1] = __int_as_float(cn);  // (a full list has kc - 1 entries at the most)
+  }
+  float acc[VEC];
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-    for (int ho = hlo; ho <= hhi; ++ho) {
-      const float wh = tap_weight(a.sh, ho, a.Hi, a.align, hi);
-      if (wh == 0.f) continue;
-      for (int wo = wlo; wo <= whi; ++wo) {
-        const float ww = tap_weight(a.sw, wo, a.Wi, a.align, wi);
-        if (ww == 0.f) continue;
-        float g[VEC];
-        Vec<T>::unpack(ldg16(GY + (((long)n * a.Ho + ho) * a.Wo + wo) * a.ldy + c0), g);
-        const float w = wh * ww;
+  for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+  for (int hb = hlo; hb <= hhi; hb += 64) {
+    if (threadIdx.x < 64) {
+      const int ho = hb + threadIdx.x;
+      const float wh = ho <= hhi ? tap_weight(a.sh, ho, a.Hi, a.align, hi) : 0.f;
+      const unsigned long long mask = __ballot(wh != 0.f);
+      const int pos = __popcll(mask & ((1ull << threadIdx.x) - 1ull));
+      if (wh != 0.f) { s_rw[pos] = wh; s_ro[pos] = ho; }
+      if (threadIdx.x == 0) s_rn = __popcll(mask);
+    }
+    __syncthreads();  // (the first one also publishes the column lists)
+    if (live) {
+      const int rn = s_rn;
+      if (use_tab) {
+        cn = __float_as_int(s_cw[sc * kc + kc - 1]);
+        const float* cw = s_cw + sc * kc;
+        const int* co = s_co + sc * kc;
+        for (int r = 0; r < rn; ++r) {
+          const float wh = s_rw[r];
+          const T* __restrict__ grow = GY + ((long)n * a.Ho + s_ro[r]) * a.Wo * a.ldy + c0;
+          // RSB_BATCH loads in flight at a time (a list of 7 is one round trip per row, not 7;
+          // slots past the end of the list repeat its last load and are not added)
+          for (int k0 = 0; k0 < cn; k0 += RSB_BATCH) {
+            uint4 q[RSB_BATCH];
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[k] = fmaf(w, g[k], acc[k]);
+            for (int u = 0; u < RSB_BATCH; ++u)
+              q[u] = ldg16(grow + (long)co[min(k0 + u, cn - 1)] * a.ldy);
+#pragma unroll
+            for (int u = 0; u < RSB_BATCH; ++u) {
+              if (k0 + u < cn) {
+                float g[VEC];
+                Vec<T>::unpack(q[u], g);
+                const float w = wh * cw[k0 + u];
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) acc[e] = fmaf(w, g[e], acc[e]);
+              }
+            }
+          }
+        }
+      } else {
+        for (int r = 0; r < rn; ++r) {
+          const float wh = s_rw[r];
+          const T* __restrict__ grow = GY + ((long)n * a.Ho + s_ro[r]) * a.Wo * a.ldy + c0;
+          for (int wo = wlo; wo <= whi; ++wo) {
+            const float ww = tap_weight(a.sw, wo, a.Wi, a.align, wi);
+            if (ww == 0.f) continue;
+            float g[VEC];
+            Vec<T>::unpack(ldg16(grow + (long)wo * a.ldy), g);
+            const float w = wh * ww;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[e] = fmaf(w, g[e], acc[e]);
+          }
+        }
       }
     }
-    stg16(GX + (((long)n * a.Hi + hi) * a.Wi + wi) * a.ldx + c0, Vec<T>::pack(acc));
+    __syncthreads();
   }
+  if (live) stg16(GX + (((long)n * a.Hi + hi) * a.Wi + wi) * a.ldx + c0, Vec<T>::pack(acc));
 }
 
 // Same, for LARGE magnifications (PSP pyramid pooling: 1x1 .. 6x6 bins -> 129x257, every source
@@ -417,13 +528,37 @@ extern "C" int seg_bilinear_fwd(int dtype, const void* x, long ldx, int N, int H
   SEG_REQUIRE(((pro_mode & PRO_AFFINE) == 0) || (pro_scale && pro_shift),
               "bilinear_fwd: missing scale/shift");
   a.mode = pro_mode; a.scale = pro_scale; a.shift = pro_shift; a.chan_mul = chan_mul;
-  const int grid = rs_grid((long)N * Ho * Wo * a.CV);
+  SEG_REQUIRE(N <= 65535 && Ho <= 65535, "bilinear_fwd: N=%d / Ho=%d beyond the launch grid", N, Ho);
+  // channel block, then the widest column segment whose source columns ((segw - 1) * scale + 3 at
+  // the outside) fit the staging buffer, spread evenly over the row
+  const int vec = dtype == DT_BF16 ? 8 : 4;
+  const int cvb = a.CV < RSF_CVB ? a.CV : RSF_CVB, ncb = (a.CV + cvb - 1) / cvb;
+  int ns_cap = RSF_LDS_FLOATS / (2 * vec * cvb);
+  long segl = a.sw > 0.f ? (long)floorf((float)(ns_cap - 3) / a.sw) + 1 : Wo;
+  int segw = (int)(segl < 1 ? 1 : (segl > RSF_MAX_SEG ? RSF_MAX_SEG : segl));
+  if (segw > Wo) segw = Wo;
+  const int nseg = (Wo + segw - 1) / segw;
+  segw = (Wo + nseg - 1) / nseg;
+  int ns_max = 1;
+  for (int s = 0; s < nseg; ++s) {  // the kernel's own float formulas, segment by segment
+    const int wo0 = s * segw, wo1 = (wo0 + segw < Wo ? wo0 + segw : Wo) - 1;
+    int s0, s1, t0, t1; float tl;
+    taps(a.sw, wo0, Wi, align_corners, s0, t1, tl);
+    taps(a.sw, wo1, Wi, align_corners, t0, s1, tl);
+    SEG_REQUIRE(s1 >= s0 && s1 - s0 + 1 <= ns_cap,
+                "bilinear_fwd: columns %d..%d read %d source columns, the block stages %d", wo0,
+                wo1, s1 - s0 + 1, ns_cap);
+    if (s1 - s0 + 1 > ns_max) ns_max = s1 - s0 + 1;
+  }
+  ns_cap = ns_max;
+  const size_t lds = (size_t)2 * ns_cap * vec * cvb * sizeof(float);
+  const dim3 grid(nseg * ncb, Ho, N);
   if (dtype == DT_BF16)
-    hipLaunchKernelGGL((bilinear_fwd_kernel<bf16_t>), dim3(grid), dim3(RS_THREADS), 0,
-                       (hipStream_t)stream, a);
+    hipLaunchKernelGGL((bilinear_fwd_kernel<bf16_t>), grid, dim3(RS_THREADS), lds,
+                       (hipStream_t)stream, a, segw, nseg, ns_cap, cvb);
   else
-    hipLaunchKernelGGL((bilinear_fwd_kernel<float>), dim3(grid), dim3(RS_THREADS), 0,
-                       (hipStream_t)stream, a);
+    hipLaunchKernelGGL((bilinear_fwd_kernel<float>), grid, dim3(RS_THREADS), lds,
+                       (hipStream_t)stream, a, segw, nseg, ns_cap, cvb);
   return check_launch("bilinear_fwd");
 }
 
@@ -448,13 +583,27 @@ extern "C" int seg_bilinear_bwd(int dtype, void* gx, long ldgx, int N, int Hi, i
                          0, (hipStream_t)stream, a);
     return check_launch("bilinear_bwd (wide)");
   }
-  const int grid = rs_grid((long)N * Hi * Wi * a.CV);
+  SEG_REQUIRE(N <= 65535 && Hi <= 65535, "bilinear_bwd: N=%d / Hi=%d beyond the launch grid", N, Hi);
+  // one source column per RS_THREADS / cvb threads; kc = the longest candidate list of a column + 1
+  const int cvb = a.CV < RSF_CVB ? a.CV : RSF_CVB, ncb = (a.CV + cvb - 1) / cvb;
+  int kc = 1;
+  for (int wi = 0; wi < Wi; ++wi) {
+    int wlo, whi;
+    cand_range(a.sw, wi, Wo, align_corners, wlo, whi);
+    if (whi - wlo + 2 > kc) kc = whi - wlo + 2;
+  }
+  int nsc = RS_THREADS / cvb;
+  const int use_tab = kc <= RSB_TAB;
+  if (use_tab && nsc > RSB_TAB / kc) nsc = RSB_TAB / kc;
+  if (nsc > Wi) nsc = Wi;
+  const int nsegs = (Wi + nsc - 1) / nsc;
+  const dim3 grid(nsegs * ncb, Hi, N);
   if (dtype == DT_BF16)
-    hipLaunchKernelGGL((bilinear_bwd_kernel<bf16_t>), dim3(grid), dim3(RS_THREADS), 0,
-                       (hipStream_t)stream, a);
+    hipLaunchKernelGGL((bilinear_bwd_kernel<bf16_t>), grid, dim3(RS_THREADS), 0,
+                       (hipStream_t)stream, a, nsc, nsegs, kc, cvb, use_tab);
   else
-    hipLaunchKernelGGL((bilinear_bwd_kernel<float>), dim3(grid), dim3(RS_THREADS), 0,
-                       (hipStream_t)stream, a);
+    hipLaunchKernelGGL((bilinear_bwd_kernel<float>), grid, dim3(RS_THREADS), 0,
+                       (hipStream_t)stream, a, nsc, nsegs, kc, cvb, use_tab);
   return check_launch("bilinear_bwd");
 }
 

@@ -5,13 +5,13 @@
 
 namespace seg {
 
-__device__ __forceinline__ float src_index(float scale, int dst, int align) {
+__host__ __device__ __forceinline__ float src_index(float scale, int dst, int align) {
   if (align) return scale * (float)dst;
   const float s = scale * ((float)dst + 0.5f) - 0.5f;
   return s < 0.f ? 0.f : s;
 }
-__device__ __forceinline__ void taps(float scale, int dst, int in, int align, int& i0, int& i1,
-                                     float& lam) {
+__host__ __device__ __forceinline__ void taps(float scale, int dst, int in, int align, int& i0,
+                                              int& i1, float& lam) {
   const float s = src_index(scale, dst, align);
   i0 = (int)s;
   if (i0 > in - 1) i0 = in - 1;
@@ -25,8 +25,8 @@ static inline float host_scale(int in, int out, int align) {
 // candidate output range [lo, hi] whose taps may touch input index i
 // (align_corners=False: src = scale*(dst+0.5)-0.5, so index i is touched up to
 //  dst < (i+1.5)/scale - 0.5 — half a source pixel further than in the aligned mapping)
-__device__ __forceinline__ void cand_range(float scale, int i, int out, int align, int& lo,
-                                           int& hi) {
+__host__ __device__ __forceinline__ void cand_range(float scale, int i, int out, int align,
+                                                    int& lo, int& hi) {
   if (scale <= 0.f) { lo = 0; hi = out - 1; return; }
   const float inv = 1.f / scale;
   lo = (int)floorf(((float)i - 1.f) * inv) - 1;

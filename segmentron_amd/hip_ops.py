@@ -948,9 +948,16 @@ def upsample_ce_bwd(lo, target, out_hw, ignore_index, loss_out, grad_out, pitch,
     H, W = out_hw
     grad_out = grad_out.reshape(1).to(torch.float32).contiguous()
     dlo = torch.empty((N, Hi, Wi, pitch), dtype=lo.dtype, device=lo.device)
+    # fp32 [N, H, Wi, C] between the row pass and the column pass (under graph capture it comes from
+    # the graph's pool like every other temporary)
+    ws_bytes = LIB.query("seg_upsample_ce_bwd_ws_bytes", N, H, Wi, C)
+    if ws_bytes < 0:
+        raise RuntimeError("upsample_ce_bwd: workspace for N=%d H=%d Wi=%d C=%d exceeds 2 GiB"
+                           % (N, H, Wi, C))
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=lo.device)
     LIB.call("seg_upsample_ce_bwd", _DT[lo.dtype], _p(lo), ld, N, Hi, Wi, C,
              _p(target.contiguous()), H, W, int(ignore_index), int(align_corners), _p(loss_out),
-             _p(grad_out), _p(dlo), pitch, _stream())
+             _p(grad_out), _p(dlo), pitch, _p(ws), ws_bytes, _stream())
     return dlo
 
 
