@@ -15,8 +15,8 @@ enum DwOp {
   DW_OP_FWD,      // forward; with reversed taps also the stride-1 data gradient
   DW_OP_DGRAD,    // strided data gradient
   DW_OP_BWD,      // fused backward
-  DW_OP_BWD_ADD,  // fused backward with a residual added in the store path
-  DW_OP_WGRAD     // weight gradient
+  DW_OP_BWD_ADD,  // fused backward with a residual added in the store path (sliding family only)
+  DW_OP_WGRAD     // separate weight gradient (tiled at dilation 1 and 2, else strip)
 };
 struct DwRoute {
   DwFamily family;
@@ -39,7 +39,8 @@ int launch_dw_slide_bwd(int dtype, const void* dy, long lddy, const void* x, lon
                         const float* sh, void* g, long ldg, float* partial_w, float* partial_bn,
                         int rows, hipStream_t st, const void* res = nullptr, long ldr = 0,
                         int res_mode = 1);  // 1: g + res, one rounding; 2: as the 2-ary sum
-// ---- LDS-tiled, stride 1, dilation 1/2
+// ---- LDS-tiled, stride 1: forward / data gradient and fused backward at dilation 2 (the launchers
+// refuse any other), weight gradient at dilation 1 and 2
 int dw_tiled_grid_y(int dtype, int C, int N, int H, int W, int kind);
 int launch_dw_tiled(int dtype, const void* x, long ldx, int N, int H, int W, int C,
                     const float* w, int w_layout, int dil, int pro_mode, const float* sc,
@@ -48,8 +49,7 @@ int launch_dw_tiled(int dtype, const void* x, long ldx, int N, int H, int W, int
 int launch_dw_bwd_tiled(int dtype, const void* dy, long lddy, const void* x, long ldx, int N, int H,
                         int W, int C, const float* w, int w_layout, int dil, int pro_mode,
                         const float* sc, const float* sh, void* g, long ldg, float* partial_w,
-                        float* partial_bn, int grid_y, hipStream_t st,
-                        const void* res = nullptr, long ldr = 0);
+                        float* partial_bn, int grid_y, hipStream_t st);
 int launch_dw_wgrad_finalize(const float* partial, int R, int C, float* out, hipStream_t st);
 int launch_dw_wgrad_tiled(int dtype, const void* x, long ldx, int N, int H, int W, int C,
                           const void* dy, long lddy, int dil, int pro_mode, const float* sc,

@@ -476,19 +476,21 @@ static int strip_gx(int CV, int& cvb_log2) {
 //                          1       3..64   row-chain   v (C, lddy), 4    [9][C]
 //                          1       > 64    strip       4                 [9][C]
 //   ... with residual      1       1       sliding     v (ldr: 4)        torch or [9][C]
-//       (one rounding, or — sliding family only — with the arithmetic of the 2-ary sum it replaces)
+//       (sliding only, no other family adds one: with one rounding, or with the arithmetic of the
+//       2-ary sum it replaces)
 //   weight gradient        1       1, 2    tiled       v                 -
 //                          other           strip       v                 -
 //
-// The sliding and row-chain families need C % 4 == 0, which every entry checks before it launches:
-// a dilation-1 launch never reaches the tiled family.  (The stride-2 fused backward has its own
-// entry point and kernel, dwconv_s2.hip: C and pitches % 4, torch taps.)
+// The sliding and row-chain families need C % 4 == 0; a launch without it falls to the strip row of
+// its op and is refused by the entry's C % vec check (4 divides every vec) before anything runs.
+// The tiled launchers refuse any dilation but 2 themselves.  (The stride-2 fused backward has its
+// own entry point and kernel, dwconv_s2.hip: C and pitches % 4, torch taps.)
 DwRoute dw_route(DwOp op, int dtype, int C, int stride, int dil) {
   const int v = dtype == DT_BF16 ? 8 : 4;
   const bool s1 = stride == 1 && op != DW_OP_DGRAD;
   DwFamily f = DW_STRIP;
   if (s1 && dil == 1 && C % 4 == 0 && op != DW_OP_WGRAD) f = DW_SLIDE;
-  else if (s1 && (dil == 1 || dil == 2)) f = DW_TILED;
+  else if (s1 && (dil == 2 || (dil == 1 && op == DW_OP_WGRAD))) f = DW_TILED;
   else if (op == DW_OP_FWD && stride == 2 && dil == 1) f = DW_TILED_S2;
   else if (s1 && dil > 2 && dil <= 64 && C % 4 == 0 && op != DW_OP_WGRAD) f = DW_ROW;
   const bool narrow = op == DW_OP_BWD && (f == DW_SLIDE || f == DW_STRIP);  // HVec: 4 channels
@@ -669,8 +671,7 @@ static int dw_bwd_fused(const char* name, int dtype, const void* dy, long lddy, 
                                  res, ldr, res_mode);
     case DW_TILED:
       return launch_dw_bwd_tiled(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, w_layout, dil, pro_mode,
-                                 pro_scale, pro_shift, g, ldg, partial_w, partial_bn, grid_y, st,
-                                 res, ldr);
+                                 pro_scale, pro_shift, g, ldg, partial_w, partial_bn, grid_y, st);
     case DW_ROW:
       return launch_dw_row_bwd(dtype, dy, lddy, x, ldx, N, H, W, C, w9c, dil, pro_mode, pro_scale,
                                pro_shift, g, ldg, partial_w, partial_bn, grid_y, st);

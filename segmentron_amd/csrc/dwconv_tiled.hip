@@ -1,16 +1,20 @@
-// LDS-tiled depthwise 3x3 (stride 1, dilation 1 or 2): forward / stride-1 data gradient (flipped
-// taps) and weight gradient.  Reference call sites: segmentron/modules/basic.py:38-40,152-153.
+// LDS-tiled depthwise 3x3.  What dw_route (dwconv.hip) sends here:
+//   stride 1, dilation 2     forward / data gradient (flipped taps) and the fused backward
+//   stride 1, dilation 1, 2  weight gradient
+//   stride 2, dilation 1     forward
+// (Every other stride-1, dilation-1 launch runs on the register-sliding kernels, dwconv_slide.hip.)
+// Reference call sites: segmentron/modules/basic.py:38-40,152-153.
 //
-// Why a second dw implementation (the strip kernels in dwconv.hip stay for stride 2 / wide
-// dilations): with one thread fetching its own 3x6 neighbourhood straight from global memory every
-// input vector crosses the L1/TA path 4.5 times and the activation is recomputed 4.5 times; on
-// MI355X that path, not HBM, was the limit (1.1-2.0 TB/s algorithmic).  Here a 256-thread block
-// owns an 8x16-pixel x 8-channel-vector tile: the (8+2d)x(16+2d) input halo tile is read from
-// global memory ONCE (16-byte vectors, 128 contiguous bytes per pixel), the producer's
-// BatchNorm(+ReLU) is applied ONCE, and the activated tile is parked in LDS in the storage
-// dtype; the 9 taps then come from LDS (ds_read_b128, rows padded by one pixel so that the two
-// rows a 16-lane phase touches hit disjoint bank halves).  Measured (tools/lab/dw_lab.hip, bf16,
-// forward + statistics): [2,65,129,728] 39.4 -> 21.2 us, [2,513,1025,128] 261 -> 137 us.
+// Why not the strip kernels of dwconv.hip: with one thread fetching its own 3x6 neighbourhood
+// straight from global memory every input vector crosses the L1/TA path 4.5 times and the
+// activation is recomputed 4.5 times; on MI355X that path, not HBM, was the limit (1.1-2.0 TB/s
+// algorithmic).  Here a 256-thread block owns an 8x16-pixel x 8-channel-vector tile: the
+// (8+2d)x(16+2d) input halo tile is read from global memory ONCE (16-byte vectors, 128 contiguous
+// bytes per pixel), the producer's BatchNorm(+ReLU) is applied ONCE, and the activated tile is
+// parked in LDS in the storage dtype; the 9 taps then come from LDS (ds_read_b128, rows padded by
+// one pixel so that the two rows a 16-lane phase touches hit disjoint bank halves).  (Measured when
+// this scheme also ran dilation 1 — tools/lab/dw_lab.hip, bf16, forward + statistics:
+// [2,65,129,728] 39.4 -> 21.2 us, [2,513,1025,128] 261 -> 137 us against the strip kernel.)
 //
 // Blocks are persistent over tiles (grid.y = number of partial rows): depthwise weights are
 // staged in LDS once, BatchNorm statistics / weight-gradient taps accumulate in registers across
@@ -21,6 +25,10 @@
 namespace seg {
 
 constexpr int LT_TH = 8, LT_TW = 16, LT_CVB = 8, LT_THREADS = 256;
+// Fused backward: remainder tiles are used only where they save at least this share (percent) of
+// the classic tile count (tiled_geom).  The 6 % was chosen against the software-pipelined
+// dilation-1 loop this file used to hold; it is kept because it decides the tiling, hence the
+// partial rows and the bits of the results.  Not re-measured for dilation 2.
 constexpr int DW_BWD_REM_PCT = 6;
 
 struct DwTiledArgs {
@@ -33,8 +41,6 @@ struct DwTiledArgs {
   const float* sc; const float* sh;
   float* partial;      // fwd: [gridDim.y][2][C] statistics or null; wgrad: [gridDim.y][9][C]
   float* partial_bn;   // fused backward: [gridDim.y][2][C] or null
-  const void* res;     // fused backward: tensor ADDED to the masked data gradient before the
-  long ldr;            // store (the other gradient of a forked activation) or null
   long ldx, ldy, lddy;
   int N, H, W, C, CV, pro_mode, tiles_h, tiles_w, ntiles;
   // r05 remainder tiling (forward / fused backward; nb = nc = 0: the classic tiling).  Tiles
@@ -184,8 +190,9 @@ __device__ __forceinline__ void tile_stage_edge(const DwTiledArgs& a, const T* _
 
 // ---- registers -> LDS: activation once per element, zero padding outside the image.
 // MODE >= 0: the prologue mode as a compile-time constant (no per-vector branches; MODE 0 stores
-// the raw vector); MODE < 0: a.pro_mode at run time.
-template <typename T, typename V, typename G, int MODE = -1>
+// the raw vector) — the fused backward stages dy with PRO_NONE; MODE < 0: a.pro_mode at run time
+// (the forward and the weight gradient).
+template <typename T, typename V, typename G, int MODE>
 __device__ __forceinline__ void tile_commit_g(const DwTiledArgs& a,
                                               typename V::raw_t* __restrict__ tile,
                                               const typename V::raw_t (&raw)[G::PER],
@@ -229,14 +236,6 @@ __device__ __forceinline__ void tile_commit_g(const DwTiledArgs& a,
       tile[(r * G::IWP + c) * LT_CVB + cx] = v;
     }
   }
-}
-
-template <typename T, typename V, int DIL, int MODE = -1>
-__device__ __forceinline__ void tile_commit(const DwTiledArgs& a,
-                                            typename V::raw_t* __restrict__ tile,
-                                            const typename V::raw_t (&raw)[TileGeom<DIL>::PER],
-                                            unsigned okmask, const float4* __restrict__ psm) {
-  tile_commit_g<T, V, TileGeom<DIL>, MODE>(a, tile, raw, okmask, psm);
 }
 
 // per-block constants -> LDS: rows 0..8 = the nine taps, rows 9/10 = prologue scale / shift
@@ -296,9 +295,10 @@ __device__ __forceinline__ LtBlock lt_block() {
   return b;
 }
 
-// One tile of the forward: halo tile -> registers -> (activation) -> LDS -> taps -> store +
-// statistics.  G: tile shape; POFF: interior 8 x 16 tiles use the per-block pixel offsets.
-template <typename T, typename G, int MODE, bool POFF>
+// One tile of the forward: halo tile -> registers -> (activation, a.pro_mode at run time) -> LDS ->
+// taps -> store + statistics.  G: tile shape; POFF: interior 8 x 16 tiles use the per-block pixel
+// offsets.
+template <typename T, typename G, bool POFF>
 __device__ __forceinline__ void dw_fwd_tile(const DwTiledArgs& a, const T* __restrict__ X,
                                             T* __restrict__ Y, uint4* __restrict__ tile,
                                             const float4* __restrict__ wsm, int n, int h0, int w0,
@@ -313,10 +313,10 @@ __device__ __forceinline__ void dw_fwd_tile(const DwTiledArgs& a, const T* __res
     unsigned okmask = 0;
     tile_issue<T, Vec<T>, DIL>(a, X, n, h0, w0, cv, raw, okmask, poff);
     __syncthreads();  // every thread is done reading the previous tile
-    tile_commit_g<T, Vec<T>, G, MODE>(a, tile, raw, okmask, wsm);
+    tile_commit_g<T, Vec<T>, G, -1>(a, tile, raw, okmask, wsm);
   } else {
     __syncthreads();
-    tile_stage_edge<T, Vec<T>, G, MODE>(a, X, tile, wsm, n, h0, w0, cv);
+    tile_stage_edge<T, Vec<T>, G, -1>(a, X, tile, wsm, n, h0, w0, cv);
   }
   __syncthreads();
 
@@ -387,7 +387,7 @@ __device__ __forceinline__ bool rem_coords(const DwTiledArgs& a, int e, int& n, 
   return false;
 }
 
-template <typename T, int DIL, int MODE = -1>
+template <typename T, int DIL>
 __global__ __launch_bounds__(LT_THREADS, sizeof(T) == 2 ? 3 : 4) void dwconv_tiled_kernel(const DwTiledArgs a) {
   using G = TileGeom<DIL>;
   constexpr int VEC = Vec<T>::N;
@@ -412,19 +412,19 @@ __global__ __launch_bounds__(LT_THREADS, sizeof(T) == 2 ? 3 : 4) void dwconv_til
   for (int i = 0; i < VEC; ++i) ssum[i] = ssq[i] = 0.f;
 
   // (a software pipeline over the tiles — the next tile's loads in flight during the taps — was
-  // measured for THIS kernel: no gain on the 24 MB tensors, -10 % on the large ones, 3 blocks/CU
-  // already overlap each other; the fused backward, 2 blocks/CU, gains 35 % from it)
+  // measured for this kernel at dilation 1: no gain on the 24 MB tensors, -10 % on the large ones,
+  // 3 blocks/CU already overlap each other)
   int poff[G::PER];
   tile_offsets<DIL>(a, poff);
   for (int t = lb.y; t < a.ntiles; t += gridDim.y) {
     int n, h0, w0, hlim = a.H;
     if (t < a.ntiles_a) {
       tile_coords(a, t, n, h0, w0);
-      dw_fwd_tile<T, G, MODE, true>(a, X, Y, tile, wsm, n, h0, w0, hlim, cv, poff, ssum, ssq);
+      dw_fwd_tile<T, G, true>(a, X, Y, tile, wsm, n, h0, w0, hlim, cv, poff, ssum, ssq);
     } else if (rem_coords(a, t - a.ntiles_a, n, h0, w0, hlim)) {
-      dw_fwd_tile<T, TileGeomB<DIL>, MODE, false>(a, X, Y, tile, wsm, n, h0, w0, hlim, cv, poff, ssum, ssq);
+      dw_fwd_tile<T, TileGeomB<DIL>, false>(a, X, Y, tile, wsm, n, h0, w0, hlim, cv, poff, ssum, ssq);
     } else {
-      dw_fwd_tile<T, TileGeomC<DIL>, MODE, false>(a, X, Y, tile, wsm, n, h0, w0, hlim, cv, poff, ssum, ssq);
+      dw_fwd_tile<T, TileGeomC<DIL>, false>(a, X, Y, tile, wsm, n, h0, w0, hlim, cv, poff, ssum, ssq);
     }
   }
 
@@ -682,7 +682,7 @@ __global__ __launch_bounds__(LT_THREADS, 2) void dwconv_wgrad_tiled_kernel(const
       if (!(rok && wo < a.W)) graw[j] = make_uint4(0u, 0u, 0u, 0u);
     }
     __syncthreads();
-    tile_commit<T, Vec<T>, DIL>(a, tile, raw, okmask, psm);
+    tile_commit_g<T, Vec<T>, G, -1>(a, tile, raw, okmask, psm);
     __syncthreads();
     float g[4][VEC];
 #pragma unroll
@@ -743,7 +743,7 @@ __global__ __launch_bounds__(LT_THREADS, 2) void dwconv_wgrad_tiled_kernel(const
 
 
 // ------------------------------------------------------------------ fused backward
-// One pass over (dy, x) for the whole depthwise backward (stride 1):
+// One pass over (dy, x) for the whole depthwise backward (stride 1, dilation 2):
 //   g'[q]   = relu_mask(x[q]) * sum_k dy[q - d_k] * w[k]      data gradient wrt act(x), masked
 //   dW[k]  += act(x[q]) * dy[q - d_k]                          the SAME shifted dy values
 //   (sum g', sum g' * x)                                       BatchNorm-backward sums of the
@@ -751,14 +751,13 @@ __global__ __launch_bounds__(LT_THREADS, 2) void dwconv_wgrad_tiled_kernel(const
 // The dy tile (+halo) is staged in LDS exactly like the forward input tile; LDS row r = kh*3+kw
 // of the staged taps holds w[8 - r] (flipped), and the value read at tile offset (kh, kw) pairs
 // with tap 8 - r of the weight gradient.  Replaces dgrad + wgrad + bn_bwd_reduce (three passes
-// over two tensors each).
-// RES: the second gradient of a forked activation (an Xception block input feeds the residual
-// sum AND the first separable conv, xception.py:40-42) is added in the store path — the
-// element-wise add autograd would launch for it (2 reads + 1 write of the tensor) is gone.
+// over two tensors each).  (A residual joining the gradient in the store path is the sliding
+// family's, dwconv_slide.hip: it is only taken at dilation 1.)
+
 // x vectors of one 4-pixel strip (one 64-bit pixel offset per tile and thread, + j * ld: the four
-// vectors used to rebuild ((n*H + h)*W + w)*ld each — with the residual loads and the stores ~150
-// VALU of address arithmetic per tile next to ~250 of tap work; only the last strip of a
-// right-border tile, a wave-uniform case, needs the column clamp)
+// vectors used to rebuild ((n*H + h)*W + w)*ld each — with the stores ~150 VALU of address
+// arithmetic per tile next to ~250 of tap work; only the last strip of a right-border tile, a
+// wave-uniform case, needs the column clamp)
 template <typename T, typename V>
 __device__ __forceinline__ void dw_bwd_issue_x(const DwTiledArgs& a, const T* __restrict__ X, int n,
                                                int h0, int w0, int row, int strip, int cv,
@@ -779,7 +778,7 @@ __device__ __forceinline__ void dw_bwd_issue_x(const DwTiledArgs& a, const T* __
 
 // The arithmetic of one tile of the fused backward: the dy halo tile is in LDS (tile), this
 // thread's four x vectors in xraw.  G: tile shape (8 x 16, or a remainder shape).
-template <typename T, typename G, bool RES>
+template <typename T, typename G>
 __device__ __forceinline__ void dw_bwd_compute(
     const DwTiledArgs& a, const typename HVec<T>::raw_t* __restrict__ tile,
     const float4* __restrict__ psm, T* __restrict__ GO, int n, int h0, int w0, int hlim, int row,
@@ -819,16 +818,6 @@ __device__ __forceinline__ void dw_bwd_compute(
   for (int j = 0; j < 4; ++j)
 #pragma unroll
     for (int i = 0; i < VEC; ++i) accg[j][i] = 0.f;
-  raw_t rres[4];
-  if (RES) {  // in flight during the tap loop
-    const T* __restrict__ R = reinterpret_cast<const T*>(a.res);
-    const int hoc = min(ho, a.H - 1), cvc = min(cv, a.CV - 1);
-    const int wb = w0 + strip * 4, wbc = min(wb, a.W - 1);
-    const T* __restrict__ pr = R + ((long)(n * a.H + hoc) * a.W + wbc) * a.ldr + cvc * VEC;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      rres[j] = V::load_raw(pr + (min(wb + j, a.W - 1) - wbc) * (int)a.ldr);
-  }
 #pragma unroll
   for (int kh = 0; kh < 3; ++kh) {
     float wv[3][VEC];
@@ -874,15 +863,7 @@ __device__ __forceinline__ void dw_bwd_compute(
           accg[j][i] = on ? accg[j][i] : 0.f;
         }
       }
-      if (RES) {
-        float rr[VEC], o[VEC];
-        V::unpack_raw(rres[j], rr);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) o[i] = accg[j][i] + rr[i];
-        V::store(pgo + j * (int)a.ldy, o);
-      } else {
-        V::store(pgo + j * (int)a.ldy, accg[j]);
-      }
+      V::store(pgo + j * (int)a.ldy, accg[j]);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         s1[i] += accg[j][i];
@@ -892,8 +873,8 @@ __device__ __forceinline__ void dw_bwd_compute(
   }
 }
 
-// one REMAINDER tile of the fused backward (no software pipeline: a block meets at most a few)
-template <typename T, typename G, bool RES>
+// one REMAINDER tile of the fused backward (staged in chunks: a block meets at most a few)
+template <typename T, typename G>
 __device__ __forceinline__ void dw_bwd_edge_tile(
     const DwTiledArgs& a, const DwTiledArgs& dyargs,
     typename HVec<T>::raw_t* __restrict__ tile, const float4* __restrict__ psm, int n, int h0,
@@ -908,13 +889,13 @@ __device__ __forceinline__ void dw_bwd_edge_tile(
   tile_stage_edge<T, V, G, PRO_NONE>(dyargs, reinterpret_cast<const T*>(a.dy), tile, psm, n, h0, w0,
                                      cv);
   __syncthreads();
-  dw_bwd_compute<T, G, RES>(a, tile, psm, reinterpret_cast<T*>(a.y), n, h0, w0, hlim, row, strip, cx,
-                            cv, xraw, sc, sh, accw, s1, s2);
+  dw_bwd_compute<T, G>(a, tile, psm, reinterpret_cast<T*>(a.y), n, h0, w0, hlim, row, strip, cx, cv,
+                       xraw, sc, sh, accw, s1, s2);
 }
 
 // REM: this launch has remainder tiles (a separate instance: with their code compiled in, the
 // 8 x 16 loop of the classic tiling spilled 12 bytes and ran 3-5 % slower on the large maps)
-template <typename T, int DIL, bool RES = false, bool REM = false>
+template <typename T, int DIL, bool REM>
 __global__ __launch_bounds__(LT_THREADS, 2) void dwconv_bwd_tiled_kernel(const DwTiledArgs a) {
   // 4 channels per thread in both element types (8-byte bf16 vectors): this kernel carries nine
   // tap accumulators per channel on top of the data-gradient accumulators
@@ -947,8 +928,9 @@ __global__ __launch_bounds__(LT_THREADS, 2) void dwconv_bwd_tiled_kernel(const D
     sc[q * 4] = s4.x; sc[q * 4 + 1] = s4.y; sc[q * 4 + 2] = s4.z; sc[q * 4 + 3] = s4.w;
     sh[q * 4] = t4.x; sh[q * 4 + 1] = t4.y; sh[q * 4 + 2] = t4.z; sh[q * 4 + 3] = t4.w;
   }
-  DwTiledArgs plain = a;  // dy is staged raw
-  plain.pro_mode = PRO_NONE;
+  DwTiledArgs dyargs = a;  // dy is staged raw, with its own pitch
+  dyargs.pro_mode = PRO_NONE;
+  dyargs.ldx = a.lddy;
 
   float accw[9][VEC], s1[VEC], s2[VEC];
 #pragma unroll
@@ -958,53 +940,34 @@ __global__ __launch_bounds__(LT_THREADS, 2) void dwconv_bwd_tiled_kernel(const D
 #pragma unroll
   for (int i = 0; i < VEC; ++i) s1[i] = s2[i] = 0.f;
 
-  // software pipeline over the block's 8 x 16 tiles (see dwconv_tiled_kernel): the next tile's dy
-  // halo tile and x vectors are in flight while the current tile is computed
-  DwTiledArgs dyargs = plain;
-  dyargs.ldx = a.lddy;
-  constexpr bool PIPE = DIL == 1;  // dilation 2 (wider halo tile) would spill with the prefetch
-  int t = lb.y, nn = 0, nh0 = 0, nw0 = 0;
+  // the block's 8 x 16 tiles, one after the other: no loads of the next tile are in flight during
+  // the taps (with the halo tile of dilation 2 in registers that prefetch would spill)
   int poff[G::PER];
   tile_offsets<DIL>(a, poff);
-  raw_t raw[G::PER], xnext[4];
-  unsigned okmask = 0;
-  if (PIPE && t < a.ntiles_a) {
-    tile_coords(a, t, nn, nh0, nw0);
-    tile_issue<T, V, DIL>(dyargs, DY, nn, nh0, nw0, cv, raw, okmask, poff);
-    dw_bwd_issue_x<T, V>(a, X, nn, nh0, nw0, row, strip, cv, xnext);
-  }
-  while (t < a.ntiles_a) {
-    if (!PIPE) {
-      tile_coords(a, t, nn, nh0, nw0);
-      tile_issue<T, V, DIL>(dyargs, DY, nn, nh0, nw0, cv, raw, okmask, poff);
-      dw_bwd_issue_x<T, V>(a, X, nn, nh0, nw0, row, strip, cv, xnext);
-    }
+  int t = lb.y;
+  for (; t < a.ntiles_a; t += gridDim.y) {
+    int n, h0, w0;
+    tile_coords(a, t, n, h0, w0);
+    raw_t raw[G::PER], xraw[4];
+    unsigned okmask = 0;
+    tile_issue<T, V, DIL>(dyargs, DY, n, h0, w0, cv, raw, okmask, poff);
+    dw_bwd_issue_x<T, V>(a, X, n, h0, w0, row, strip, cv, xraw);
+    __syncthreads();  // every thread is done reading the previous tile
+    tile_commit_g<T, V, G, PRO_NONE>(dyargs, tile, raw, okmask, psm);
     __syncthreads();
-    tile_commit<T, V, DIL, PRO_NONE>(plain, tile, raw, okmask, psm);
-    const int n = nn, h0 = nh0, w0 = nw0;
-    raw_t xraw[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) xraw[j] = xnext[j];
-    t += gridDim.y;
-    if (PIPE && t < a.ntiles_a) {
-      tile_coords(a, t, nn, nh0, nw0);
-      tile_issue<T, V, DIL>(dyargs, DY, nn, nh0, nw0, cv, raw, okmask, poff);
-      dw_bwd_issue_x<T, V>(a, X, nn, nh0, nw0, row, strip, cv, xnext);
-    }
-    __syncthreads();
-    dw_bwd_compute<T, G, RES>(a, tile, psm, GO, n, h0, w0, a.H, row, strip, cx, cv, xraw, sc, sh,
-                              accw, s1, s2);
+    dw_bwd_compute<T, G>(a, tile, psm, GO, n, h0, w0, a.H, row, strip, cx, cv, xraw, sc, sh, accw,
+                         s1, s2);
   }
   // remainder tiles (t continues behind the 8 x 16 tiles with the same stride)
   if constexpr (REM)
   for (; t < a.ntiles; t += gridDim.y) {
     int n, h0, w0, hlim;
     if (rem_coords(a, t - a.ntiles_a, n, h0, w0, hlim))
-      dw_bwd_edge_tile<T, TileGeomB<DIL>, RES>(a, dyargs, tile, psm, n, h0, w0, hlim, cx, cv,
-                                               sc, sh, accw, s1, s2);
+      dw_bwd_edge_tile<T, TileGeomB<DIL>>(a, dyargs, tile, psm, n, h0, w0, hlim, cx, cv, sc, sh,
+                                          accw, s1, s2);
     else
-      dw_bwd_edge_tile<T, TileGeomC<DIL>, RES>(a, dyargs, tile, psm, n, h0, w0, hlim, cx, cv,
-                                               sc, sh, accw, s1, s2);
+      dw_bwd_edge_tile<T, TileGeomC<DIL>>(a, dyargs, tile, psm, n, h0, w0, hlim, cx, cv, sc, sh,
+                                          accw, s1, s2);
   }
 
   // ---- block reductions (rows of a wave by lane exchange, strips through LDS)
@@ -1088,7 +1051,7 @@ int launch_dw_wgrad_finalize(const float* partial, int R, int C, float* out, hip
 // rem: the r05 tiling with remainder tiles (forward / fused backward); the weight-gradient kernel
 // keeps the classic one
 // rem_pct: minimum share (percent) of the classic tile count the remainder tiles must save
-// (the fused backward: 6 — below that its pipelined 8 x 16 loop on the classic tiling wins)
+// (the fused backward: DW_BWD_REM_PCT)
 static void tiled_geom(DwTiledArgs& a, int dtype, int N, int H, int W, int C, bool rem = false,
                        int rem_pct = 0) {
   const int vec = dtype == DT_BF16 ? 8 : 4;
@@ -1116,11 +1079,11 @@ static void tiled_geom(DwTiledArgs& a, int dtype, int N, int H, int W, int C, bo
 }
 
 // Persistent blocks: about one resident set of blocks for the whole launch (3 per CU forward, 2 per
-// CU fused backward), each walking several tiles so that the tile pipeline has something to
-// overlap; the count also bounds the number of partial rows.
+// CU fused backward), each walking several tiles; the count also bounds the number of partial
+// rows, so the caps below decide result bits and stay as they were measured.
 int dw_tiled_grid_y(int dtype, int C, int N, int H, int W, int kind) {
   // kind 0: forward / dgrad (one tile per block where possible: 3 blocks/CU overlap each other),
-  // 1: fused backward (two resident blocks per CU, several tiles each for the tile pipeline),
+  // 1: fused backward (two resident blocks per CU, several tiles each),
   // 2: weight gradient (few partial rows: its block reduction is the expensive part)
   DwTiledArgs a;
   tiled_geom(a, dtype, N, H, W, C, kind != 2, kind == 1 ? DW_BWD_REM_PCT : 0);
@@ -1137,7 +1100,7 @@ int dw_tiled_grid_y(int dtype, int C, int N, int H, int W, int kind) {
   return (int)gy;
 }
 
-template <int DIL> static size_t tiled_lds(int dtype, bool with_weights, int nb = 0, int nc = 0) {
+template <int DIL> static size_t tiled_lds(int dtype, int nb = 0, int nc = 0) {
   const int vec = dtype == DT_BF16 ? 8 : 4;
   // (the kernels place the parameter rows behind the largest tile image of the launch)
   size_t b = (size_t)(nb ? TileGeomB<DIL>::TILE_VECS : nc ? TileGeomC<DIL>::TILE_VECS
@@ -1146,7 +1109,6 @@ template <int DIL> static size_t tiled_lds(int dtype, bool with_weights, int nb 
   const size_t red_wg = (size_t)4 * LT_CVB * 11 * vec * sizeof(float);
   if (b < red_fwd) b = red_fwd;
   if (b < red_wg) b = red_wg;
-  (void)with_weights;
   b += (size_t)11 * LT_CVB * vec * sizeof(float);  // taps + prologue scale / shift
   return b;
 }
@@ -1175,7 +1137,7 @@ int launch_dw_tiled_s2(int dtype, const void* x, long ldx, int N, int H, int W, 
   a.ntiles = N * a.tiles_h * a.tiles_w;
   a.w_layout = w_layout;
   a.x = x; a.w = w; a.y = y; a.dy = nullptr; a.sc = sc; a.sh = sh; a.partial = stat_partial;
-  a.partial_bn = nullptr; a.res = nullptr; a.ldr = 0;
+  a.partial_bn = nullptr;
   a.ldx = ldx; a.ldy = ldy; a.lddy = 0; a.pro_mode = pro_mode;
   const dim3 grid((a.CV + LT_CVB - 1) / LT_CVB, grid_y);
   size_t lds = (size_t)S2Geom::TILE_VECS * 16;
@@ -1197,35 +1159,24 @@ int launch_dw_tiled_s2(int dtype, const void* x, long ldx, int N, int H, int W, 
   return check_launch("dwconv3x3 (tiled, stride 2)");
 }
 
+// forward / data gradient (flipped taps), dilation 2
 int launch_dw_tiled(int dtype, const void* x, long ldx, int N, int H, int W, int C,
                     const float* w, int w_layout, int dil, int pro_mode, const float* sc,
                     const float* sh, void* y, long ldy, float* stat_partial, int grid_y,
                     hipStream_t st) {
+  SEG_REQUIRE(dil == 2, "dwconv3x3 (tiled): dilation %d has no tiled kernel", dil);
   DwTiledArgs a;
   tiled_geom(a, dtype, N, H, W, C, true);
   a.w_layout = w_layout;
   a.x = x; a.w = w; a.y = y; a.dy = nullptr; a.sc = sc; a.sh = sh; a.partial = stat_partial;
-  a.partial_bn = nullptr; a.res = nullptr; a.ldr = 0;
+  a.partial_bn = nullptr;
   a.ldx = ldx; a.ldy = ldy; a.lddy = 0; a.pro_mode = pro_mode;
   const dim3 grid((a.CV + LT_CVB - 1) / LT_CVB, grid_y);
-#define SEG_LT(TT, DD, MM) \
-  hipLaunchKernelGGL((dwconv_tiled_kernel<TT, DD, MM>), grid, dim3(LT_THREADS), \
-                     tiled_lds<DD>(dtype, true, a.nb, a.nc), st, a)
-  if (dtype == DT_BF16 && dil == 1) {
-    // the prologue modes of the networks as compile-time constants (no per-vector branches)
-    switch (pro_mode) {
-      case PRO_NONE: SEG_LT(bf16_t, 1, PRO_NONE); break;
-      case PRO_RELU: SEG_LT(bf16_t, 1, PRO_RELU); break;
-      case PRO_AFFINE: SEG_LT(bf16_t, 1, PRO_AFFINE); break;
-      case PRO_AFFINE_RELU: SEG_LT(bf16_t, 1, PRO_AFFINE_RELU); break;
-      default: SEG_LT(bf16_t, 1, -1); break;
-    }
-  } else if (dtype == DT_BF16) {
-    SEG_LT(bf16_t, 2, -1);
-  } else {
-    if (dil == 1) SEG_LT(float, 1, -1); else SEG_LT(float, 2, -1);
-  }
-#undef SEG_LT
+  const size_t lds = tiled_lds<2>(dtype, a.nb, a.nc);
+  if (dtype == DT_BF16)
+    hipLaunchKernelGGL((dwconv_tiled_kernel<bf16_t, 2>), grid, dim3(LT_THREADS), lds, st, a);
+  else
+    hipLaunchKernelGGL((dwconv_tiled_kernel<float, 2>), grid, dim3(LT_THREADS), lds, st, a);
   return check_launch("dwconv3x3 (tiled)");
 }
 
@@ -1236,45 +1187,40 @@ int launch_dw_wgrad_tiled(int dtype, const void* x, long ldx, int N, int H, int 
   tiled_geom(a, dtype, N, H, W, C);
   a.w_layout = 0;
   a.x = x; a.w = nullptr; a.y = nullptr; a.dy = dy; a.sc = sc; a.sh = sh; a.partial = partial;
-  a.partial_bn = nullptr; a.res = nullptr; a.ldr = 0;
+  a.partial_bn = nullptr;
   a.ldx = ldx; a.ldy = 0; a.lddy = lddy; a.pro_mode = pro_mode;
   const dim3 grid((a.CV + LT_CVB - 1) / LT_CVB, grid_y);
 #define SEG_LT(TT, DD) \
   hipLaunchKernelGGL((dwconv_wgrad_tiled_kernel<TT, DD>), grid, dim3(LT_THREADS), \
-                     tiled_lds<DD>(dtype, false), st, a)
+                     tiled_lds<DD>(dtype), st, a)
   if (dtype == DT_BF16) { if (dil == 1) SEG_LT(bf16_t, 1); else SEG_LT(bf16_t, 2); }
   else { if (dil == 1) SEG_LT(float, 1); else SEG_LT(float, 2); }
 #undef SEG_LT
   return check_launch("dwconv3x3_wgrad (tiled)");
 }
 
-
+// fused backward, dilation 2
 int launch_dw_bwd_tiled(int dtype, const void* dy, long lddy, const void* x, long ldx, int N, int H,
                         int W, int C, const float* w, int w_layout, int dil, int pro_mode,
                         const float* sc, const float* sh, void* g, long ldg, float* partial_w,
-                        float* partial_bn, int grid_y, hipStream_t st, const void* res, long ldr) {
+                        float* partial_bn, int grid_y, hipStream_t st) {
+  SEG_REQUIRE(dil == 2, "dwconv3x3_bwd_fused (tiled): dilation %d has no tiled kernel", dil);
   DwTiledArgs a;
   tiled_geom(a, dtype, N, H, W, C, true, DW_BWD_REM_PCT);
   a.CV = C / 4;               // HVec: 4 channels per thread in both element types
   a.w_layout = w_layout ^ 2;  // taps staged flipped (bit 1 toggles the caller's orientation)
   a.x = x; a.w = w; a.y = g; a.dy = dy; a.sc = sc; a.sh = sh;
   a.partial = partial_w; a.partial_bn = partial_bn;
-  a.res = res; a.ldr = ldr;
   a.ldx = ldx; a.ldy = ldg; a.lddy = lddy; a.pro_mode = pro_mode;
   const dim3 grid((a.CV + LT_CVB - 1) / LT_CVB, grid_y);
-#define SEG_LT(TT, DD, RR)                                                                       \
-  do {                                                                                           \
-    if (a.nb || a.nc)                                                                            \
-      hipLaunchKernelGGL((dwconv_bwd_tiled_kernel<TT, DD, RR, true>), grid, dim3(LT_THREADS),    \
-                         tiled_lds<DD>(dtype, true, a.nb, a.nc), st, a);                         \
-    else                                                                                         \
-      hipLaunchKernelGGL((dwconv_bwd_tiled_kernel<TT, DD, RR, false>), grid, dim3(LT_THREADS),   \
-                         tiled_lds<DD>(dtype, true), st, a);                                     \
-  } while (0)
-  if (res != nullptr) {  // (dilation 1 only)
-    if (dtype == DT_BF16) SEG_LT(bf16_t, 1, true); else SEG_LT(float, 1, true);
-  } else if (dtype == DT_BF16) { if (dil == 1) SEG_LT(bf16_t, 1, false); else SEG_LT(bf16_t, 2, false); }
-  else { if (dil == 1) SEG_LT(float, 1, false); else SEG_LT(float, 2, false); }
+  const size_t lds = tiled_lds<2>(dtype, a.nb, a.nc);
+#define SEG_LT(TT, REM) \
+  hipLaunchKernelGGL((dwconv_bwd_tiled_kernel<TT, 2, REM>), grid, dim3(LT_THREADS), lds, st, a)
+  if (a.nb || a.nc) {
+    if (dtype == DT_BF16) SEG_LT(bf16_t, true); else SEG_LT(float, true);
+  } else {
+    if (dtype == DT_BF16) SEG_LT(bf16_t, false); else SEG_LT(float, false);
+  }
 #undef SEG_LT
   return check_launch("dwconv3x3_bwd_fused (tiled)");
 }

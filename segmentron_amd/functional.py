@@ -527,6 +527,14 @@ def _dw_taps(weight, stride, dil, reversed=False):
                        lambda: pack_dw_weight(weight, reversed))
 
 
+def _dw_bwd_is_fused(stride, dil, C, wdtype):
+    """Is this depthwise layer's backward the one-pass kind (masked data gradient, weight-gradient
+    partials and BatchNorm sums from one launch)?  Every stride-1 layer, and stride 2 / dilation 1
+    on its own kernel (csrc/dwconv_s2.hip).  _DwFn.backward runs by it and low_feat_fork arms a
+    fork on it: one statement, so that the two cannot drift."""
+    return stride == 1 or (stride == 2 and dil == 1 and C % 4 == 0 and wdtype == torch.float32)
+
+
 def _round_up(v, m):
     return (v + m - 1) // m * m
 
@@ -750,11 +758,11 @@ class _DwFn(torch.autograd.Function):
         if f is not None:
             f.closed = True  # (a consumer that runs after this one keeps its gradient)
         tiled = K.dw_tiled(s.stride, s.dil)  # these kernels produce dW in torch's layout, too
-        # One pass over (dy, x): masked data gradient + weight-gradient partials + BN sums — every
-        # stride-1 layer, and stride 2 / dilation 1 on its own kernel (csrc/dwconv_s2.hip).
-        # Otherwise: weight gradient and data gradient separately.
-        fused_s2 = s.stride == 2 and s.dil == 1 and C % 4 == 0 and weight.dtype == torch.float32
-        if ctx.needs_input_grad[0] and (s.stride == 1 or fused_s2):
+        # One pass over (dy, x): masked data gradient + weight-gradient partials + BN sums
+        # (_dw_bwd_is_fused).  Otherwise: weight gradient and data gradient separately.
+        fused = _dw_bwd_is_fused(s.stride, s.dil, C, weight.dtype)
+        fused_s2 = fused and s.stride == 2
+        if ctx.needs_input_grad[0] and fused:
             # raw: leave the weight-gradient partials to the launch that reduces the
             # BatchNorm-backward ones (single-process BatchNorm, or SyncBatchNorm on the mailbox)
             raw = bn is not None and (fused_s2 or tiled) and \
@@ -1586,9 +1594,8 @@ def low_feat_fork(act, dw):
     if not (torch.is_grad_enabled() and t.requires_grad) or t.dim() != 4:
         return None
     C, s, d = t.shape[-1], dw.stride[0], dw.dilation[0]
-    fused = s == 1 or (s == 2 and d == 1 and C % 4 == 0 and dw.weight.dtype == torch.float32)
-    if not fused or C % K.vec_of(t.dtype) != 0 or act.relu or act.bn is None \
-            or not _bn_backward_is_plain(act.bn):
+    if not _dw_bwd_is_fused(s, d, C, dw.weight.dtype) or C % K.vec_of(t.dtype) != 0 \
+            or act.relu or act.bn is None or not _bn_backward_is_plain(act.bn):
         return None
     return GradFork(GradFork.RAW)
 

@@ -215,8 +215,10 @@ def conv_wgrad(x, dy, O, KH, KW, stride, pad, dil, pro=None, raw_partial=False):
 
 # ----------------------------------------------------------------------------- depthwise
 def dw_tiled(stride, dil):
-    """True where the LDS-tiled depthwise kernels run: they read the taps in torch's own
-    [C,1,3,3] layout (no repacking) and, for the data gradient, reversed in place."""
+    """True where the depthwise kernels take torch's tap layout — stride 1 at dilation 1 (the
+    register-sliding kernels; the separate weight gradient is LDS-tiled) and at dilation 2 (the
+    LDS-tiled ones): they read the taps as the [C,1,3,3] parameter holds them (no repacking) and,
+    for the data gradient, reversed in place."""
     return stride == 1 and dil in (1, 2)
 
 
