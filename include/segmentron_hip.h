@@ -419,6 +419,31 @@ int seg_upsample_ce_bwd(int dtype, const void* lo, long ld, int N, int Hi, int W
                         const float* loss_out, const float* grad_out, void* dlo, long lddlo,
                         float* ws, long ws_bytes, void* stream);
 
+/* ---- DUpsampling (segmentron/models/dunet.py:90-117) on the low-resolution NHWC tensor ---------
+ * lo: [N, h, w, ld] output of the module's 1x1 convolution in `dtype`, s*s*C valid channels
+ * (1 <= C <= 32 classes, s >= 1, ld >= s*s*C and a multiple of the 16-byte vector).  The
+ * reference's three permute / view rounds amount to
+ *     out[n, k, hh*s + a, ww*s + b] = lo[n, hh, ww, (a*s + b)*C + k]
+ * seg_dup_ce_fwd/bwd: F.cross_entropy(out, target, ignore_index), mean over valid pixels, on lo
+ * itself; target int64 [N, h*s, w*s] read in place; loss_out float32[2] = (mean loss, 1 / valid
+ * count), NaN and 0 when no pixel is valid; labels outside [0, C) are ignored too; ws >= 2 *
+ * seg_dup_ce_blocks(...) doubles (-1: bad geometry).  dlo [N, h, w, lddlo] in `dtype` =
+ * grad_out[0] * loss_out[1] * (softmax - onehot), zeros for invalid pixels and for channels >=
+ * s*s*C.  Arithmetic of seg_point_ce_fwd/bwd; deterministic, no atomics.
+ * seg_dup_to_nchw: the materialised float32 [N, C, h*s, w*s]; seg_dup_to_nchw_bwd: its inverse,
+ * float32 NCHW gradient gy -> gx [N, h, w, ldgx] in `dtype` (pad channels zero). */
+int seg_dup_ce_blocks(int dtype, long ld, int N, int h, int w, int s, int C);
+int seg_dup_ce_fwd(int dtype, const void* lo, long ld, int N, int h, int w, int s, int C,
+                   const long* target, long ignore_index, double* ws, float* loss_out,
+                   void* stream);
+int seg_dup_ce_bwd(int dtype, const void* lo, long ld, int N, int h, int w, int s, int C,
+                   const long* target, long ignore_index, const float* loss_out,
+                   const float* grad_out, void* dlo, long lddlo, void* stream);
+int seg_dup_to_nchw(int dtype, const void* lo, long ld, int N, int h, int w, int s, int C,
+                    float* out, void* stream);
+int seg_dup_to_nchw_bwd(int dtype, void* gx, long ldgx, int N, int h, int w, int s, int C,
+                        const float* gy, void* stream);
+
 /* ---- PointRend point head (segmentron/models/pointrend.py:32-195, csrc/pointrend.hip) ---------
  * Maps are addressed through strides: element (n, pixel h*W + w, channel c) at
  * x + n*sn + (h*W + w)*sp + c*sc (NHWC activation: sn = H*W*ld, sp = ld, sc = 1; NCHW float32:

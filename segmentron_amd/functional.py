@@ -995,6 +995,11 @@ class LogitsView:
     def __post_init__(self):
         self.out_hw = tuple(int(v) for v in self.out_hw)
 
+    @property
+    def view_args(self):
+        """type(view)(other_lo, *view.view_args): the same view of another tensor (graph.py)."""
+        return (self.out_hw, self.align_corners, self.max_scale)
+
     # -- cheap metadata, no materialisation
     @property
     def shape(self):
@@ -1068,6 +1073,139 @@ class LogitsView:
                 return type(o)(real(v) for v in o)
             return o
         return func(*real(args), **{k: real(v) for k, v in kwargs.items()})
+
+
+class _DupLogitsFn(torch.autograd.Function):
+    """Model boundary of DUNet: the NHWC output [N, h, w, s*s*C] of DUpsampling's 1x1 convolution
+    -> the module's NCHW float32 [N, C, h*s, w*s] (dunet.py:98-117), pure data movement both
+    ways (csrc/dupsample.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, scale, nclass):
+        ctx.meta = (x.dtype, scale)
+        return K.dup_to_nchw(x, scale, nclass)
+
+    @staticmethod
+    def backward(ctx, g):
+        dtype, scale = ctx.meta
+        k = scale * scale * g.shape[1]
+        gx = K.dup_to_nchw_bwd(g, scale, dtype)
+        return gx[..., :k], None, None
+
+
+def dup_fused_cross_entropy(lo, target, scale, nclass, ignore_index):
+    """F.cross_entropy(DUpsampling(lo), target, ignore_index) with reduction='mean', fused on the
+    low-resolution tensor (csrc/dupsample.hip), through the registered custom operator
+    `torch.ops.segmentron_hip.dupsample_cross_entropy` (segmentron_amd/torch_ops.py)."""
+    out = torch.ops.segmentron_hip.dupsample_cross_entropy(lo, target, int(scale), int(nclass),
+                                                           int(ignore_index))
+    return out[0]
+
+
+@dataclasses.dataclass(eq=False, repr=False)
+class DUpLogitsView:
+    """LogitsView's sibling for DUNet: what the model returns per head in training mode instead
+    of DUpsampling's [N, nclass, h*scale, w*scale] float32 tensor — `lo`, the NHWC output
+    [N, h, w, scale*scale*nclass] of the module's 1x1 convolution, whose rearrangement
+        out[n, k, hh*s + a, ww*s + b] = lo[n, hh, ww, (a*s + b)*nclass + k]
+    is pending.  `F.cross_entropy` / `nn.CrossEntropyLoss` (mean reduction, no class weights, no
+    label smoothing, int64 target [N, h*s, w*s], nclass <= 32) run fused on `lo`; everything else
+    materialises the tensor once (seg_dup_to_nchw, differentiable) and forwards to it.  A
+    dataclass, like LogitsView, so that DistributedDataParallel finds `lo`."""
+    lo: torch.Tensor
+    scale: int
+    nclass: int
+    _full: object = dataclasses.field(default=None, init=False, repr=False)
+
+    def __post_init__(self):
+        self.scale, self.nclass = int(self.scale), int(self.nclass)
+        if self.lo.dim() != 4 or self.lo.shape[-1] != self.scale * self.scale * self.nclass:
+            raise ValueError("DUpLogitsView: %s is not [N, h, w, %d*%d*%d]"
+                             % (tuple(self.lo.shape), self.scale, self.scale, self.nclass))
+
+    @property
+    def out_hw(self):
+        return (self.lo.shape[1] * self.scale, self.lo.shape[2] * self.scale)
+
+    @property
+    def view_args(self):
+        """type(view)(other_lo, *view.view_args): the same view of another tensor (graph.py)."""
+        return (self.scale, self.nclass)
+
+    # -- cheap metadata, no materialisation
+    @property
+    def shape(self):
+        return torch.Size((self.lo.shape[0], self.nclass) + self.out_hw)
+
+    def size(self, dim=None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def dim(self):
+        return 4
+
+    dtype = torch.float32
+
+    @property
+    def device(self):
+        return self.lo.device
+
+    @property
+    def requires_grad(self):
+        return self.lo.requires_grad
+
+    def materialize(self):
+        if self._full is None:
+            self._full = _DupLogitsFn.apply(self.lo, self.scale, self.nclass)
+        return self._full
+
+    def __getattr__(self, name):  # only called when normal lookup fails
+        if name.startswith("__") and name.endswith("__"):
+            raise AttributeError(name)
+        return getattr(self.materialize(), name)
+
+    def __getitem__(self, idx):
+        return self.materialize()[idx]
+
+    def __len__(self):
+        return self.lo.shape[0]
+
+    def _fusable(self, target, weight, size_average, ignore_index, reduce, reduction,
+                 label_smoothing):
+        return (weight is None and size_average is None and reduce is None
+                and reduction == "mean" and label_smoothing == 0.0 and self.nclass <= 32
+                and isinstance(target, torch.Tensor) and target.dtype == torch.int64
+                and target.dim() == 3
+                and tuple(target.shape) == (self.lo.shape[0],) + self.out_hw)
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        if func is torch.nn.functional.cross_entropy and args and isinstance(args[0], cls):
+            def bind(input, target, weight=None, size_average=None, ignore_index=-100,
+                     reduce=None, reduction="mean", label_smoothing=0.0):
+                return target, weight, size_average, ignore_index, reduce, reduction, \
+                    label_smoothing
+            b = bind(*args, **kwargs)
+            view = args[0]
+            if view._fusable(*b):
+                return dup_fused_cross_entropy(view.lo, b[0], view.scale, view.nclass, int(b[3]))
+
+        def real(o):
+            if isinstance(o, cls):
+                return o.materialize()
+            if isinstance(o, (list, tuple)):
+                return type(o)(real(v) for v in o)
+            return o
+        return func(*real(args), **{k: real(v) for k, v in kwargs.items()})
+
+
+def dup_logits(x, s, nclass, lazy=False):
+    """DUNet's model boundary.  x: NHWC [N, h, w, s*s*nclass].  lazy (training): a DUpLogitsView,
+    so that a following cross-entropy runs fused on x; otherwise DUpsampling's materialised
+    [N, nclass, h*s, w*s] float32 tensor."""
+    if lazy:
+        return DUpLogitsView(x, s, nclass)
+    return _DupLogitsFn.apply(x, int(s), int(nclass))
 
 
 class _GapFn(torch.autograd.Function):

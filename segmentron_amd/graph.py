@@ -139,6 +139,19 @@ class GraphedTrainStep:
 
 
 # ----------------------------------------------------------------------------- transparent capture
+_VIEWS = (F.LogitsView, F.DUpLogitsView)  # lazy model outputs: `.lo` + `.view_args`
+
+
+def _view_meta(o):
+    """(class, arguments) that rebuild a lazy output around another tensor, None for a tensor.
+    The class is the entry of _VIEWS the output is an instance of (a subclass of LogitsView comes
+    back as a LogitsView, as it always has)."""
+    for cls in _VIEWS:
+        if isinstance(o, cls):
+            return cls, o.view_args
+    return None
+
+
 class _GraphedSegment(torch.autograd.Function):
     """One captured forward / backward pair as an autograd node (the torch.cuda
     make_graphed_callables split): forward replays the forward graph and hands out the static
@@ -324,7 +337,7 @@ class TransparentTrainGraph:
             self.segments[key] = seg
         seg.x.copy_(x)
         lo = _GraphedSegment.apply(seg.anchor, seg)
-        return seg.container(t if m is None else F.LogitsView(t, *m)
+        return seg.container(t if m is None else m[0](t, *m[1])
                              for t, m in zip(lo, seg.meta))
 
     # -- capture of one shape
@@ -360,14 +373,15 @@ class TransparentTrainGraph:
             with F.restrict_pack_plan(seg.params), capture(seg.fwd):
                 outs = torch.func.functional_call(
                     model, {n: t for (n, _), t in zip(named, leaves)}, (seg.x,))
-            # outputs: LogitsView (low-resolution logits, upsampled inside the fused loss) or a
-            # materialised tensor (HRNet's align_corners=False boundary)
-            if not all(isinstance(o, (F.LogitsView, torch.Tensor)) for o in outs):
+            # outputs: LogitsView (low-resolution logits, upsampled inside the fused loss),
+            # DUpLogitsView (DUNet: rearranged inside its fused loss) or a materialised tensor
+            # (HRNet's align_corners=False boundary); a view is rebuilt around the static tensor
+            # from its class and `view_args`
+            if not all(isinstance(o, _VIEWS + (torch.Tensor,)) for o in outs):
                 raise RuntimeError("transparent capture needs tensor / LogitsView outputs")
             seg.container = list if isinstance(outs, list) else tuple
-            seg.lo = [o.lo if isinstance(o, F.LogitsView) else o for o in outs]
-            seg.meta = [(o.out_hw, o.align_corners, o.max_scale) if isinstance(o, F.LogitsView)
-                        else None for o in outs]
+            seg.lo = [o.lo if isinstance(o, _VIEWS) else o for o in outs]
+            seg.meta = [_view_meta(o) for o in outs]
             seg.grad_lo = [torch.zeros_like(t) for t in seg.lo]
             with F.restrict_pack_plan(seg.params), capture(seg.bwd):
                 grads = torch.autograd.grad(seg.lo, leaves, seg.grad_lo, allow_unused=True)

@@ -963,6 +963,70 @@ def upsample_ce_bwd(lo, target, out_hw, ignore_index, loss_out, grad_out, pitch,
     return dlo
 
 
+# ----------------------------------------------------------------------------- DUpsampling
+def _dup_geometry(lo, s, C, what):
+    """-> (N, h, w, ld) of the NHWC output of DUpsampling's 1x1 convolution (s*s*C channels)."""
+    N, h, w, K, ld = nhwc(lo)
+    if lo.dtype not in _DT:
+        raise RuntimeError("%s: float32 or bfloat16 logits, got %s" % (what, lo.dtype))
+    if K != s * s * C:
+        raise RuntimeError("%s: %d channels are not s*s*C = %d*%d*%d" % (what, K, s, s, C))
+    return N, h, w, ld
+
+
+def dup_ce_fwd(lo, target, s, C, ignore_index):
+    """F.cross_entropy(DUpsampling(lo), target, ignore_index) on the low-resolution NHWC tensor
+    lo [N, h, w, s*s*C]; target int64 [N, h*s, w*s].  -> float32[2] device tensor (mean loss over
+    the valid pixels, 1 / valid count)."""
+    N, h, w, ld = _dup_geometry(lo, s, C, "dup_ce")
+    if not target.is_cuda or target.dtype != torch.int64 \
+            or tuple(target.shape) != (N, h * s, w * s):
+        raise RuntimeError("dup_ce: target must be an int64 HIP tensor [N, H, W] = %s, got %s"
+                           % ((N, h * s, w * s), tuple(target.shape)))
+    blocks = LIB.query("seg_dup_ce_blocks", _DT[lo.dtype], ld, N, h, w, s, C)
+    ws = torch.empty(2 * max(blocks, 1), dtype=torch.float64, device=lo.device)
+    out = torch.empty(2, dtype=torch.float32, device=lo.device)
+    LIB.call("seg_dup_ce_fwd", _DT[lo.dtype], _p(lo), ld, N, h, w, s, C, _p(target.contiguous()),
+             int(ignore_index), _p(ws), _p(out), _stream())
+    return out
+
+
+def dup_ce_bwd(lo, target, s, C, ignore_index, loss_out, grad_out, pitch=None):
+    """-> d(loss)/d(lo) * grad_out as NHWC [N, h, w, pitch] in lo.dtype (channels >= s*s*C and
+    the rows of invalid pixels are zero); pitch defaults to s*s*C rounded up to a vector."""
+    N, h, w, ld = _dup_geometry(lo, s, C, "dup_ce_bwd")
+    vec = vec_of(lo.dtype)
+    pitch = pitch or (s * s * C + vec - 1) // vec * vec
+    grad_out = grad_out.reshape(1).to(torch.float32).contiguous()
+    dlo = torch.empty((N, h, w, pitch), dtype=lo.dtype, device=lo.device)
+    LIB.call("seg_dup_ce_bwd", _DT[lo.dtype], _p(lo), ld, N, h, w, s, C, _p(target.contiguous()),
+             int(ignore_index), _p(loss_out), _p(grad_out), _p(dlo), pitch, _stream())
+    return dlo
+
+
+def dup_to_nchw(lo, s, C):
+    """lo NHWC [N, h, w, s*s*C] -> DUpsampling's float32 NCHW [N, C, h*s, w*s]."""
+    N, h, w, ld = _dup_geometry(lo, s, C, "dup_to_nchw")
+    out = torch.empty((N, C, h * s, w * s), dtype=torch.float32, device=lo.device)
+    LIB.call("seg_dup_to_nchw", _DT[lo.dtype], _p(lo), ld, N, h, w, s, C, _p(out), _stream())
+    return out
+
+
+def dup_to_nchw_bwd(gy, s, dtype, pitch=None):
+    """gy float32 NCHW [N, C, h*s, w*s] -> NHWC [N, h, w, pitch] of `dtype` (pad channels zero)."""
+    if not gy.is_cuda or gy.dtype != torch.float32 or gy.dim() != 4:
+        raise RuntimeError("dup_to_nchw_bwd needs a float32 HIP device tensor [N, C, H, W]")
+    N, C, H, W = gy.shape
+    if H % s or W % s:
+        raise RuntimeError("dup_to_nchw_bwd: %d x %d is not a multiple of s = %d" % (H, W, s))
+    vec = vec_of(dtype)
+    pitch = pitch or (s * s * C + vec - 1) // vec * vec
+    gx = torch.empty((N, H // s, W // s, pitch), dtype=dtype, device=gy.device)
+    LIB.call("seg_dup_to_nchw_bwd", _DT[dtype], _p(gx), pitch, N, H // s, W // s, s, C,
+             _p(gy.contiguous()), _stream())
+    return gx
+
+
 # ----------------------------------------------------------------------------- optimizer
 def sgd_check(p, g, b):
     if not (p.is_cuda and g.is_cuda and b.is_cuda):

@@ -9,3 +9,4 @@ from .fast_scnn import FastSCNN  # noqa: F401
 from .danet import DANet  # noqa: F401
 from .pointrend import PointRend  # noqa: F401
 from .bisenet import BiSeNet  # noqa: F401
+from .dunet import DUNet  # noqa: F401

@@ -14,6 +14,8 @@ layouts — the same conventions as the C-ABI (include/segmentron_hip.h).
     y  = torch.ops.segmentron_hip.interpolate_bilinear(x, out_h, out_w, align_corners)
     lo = torch.ops.segmentron_hip.upsample_cross_entropy(logits, target, out_h, out_w,
                                                          ignore_index, align_corners)   # [2]
+    lo = torch.ops.segmentron_hip.dupsample_cross_entropy(logits, target, scale, nclass,
+                                                          ignore_index)                  # [2]
     out, att, raw = torch.ops.segmentron_hip.criss_cross_attention(q, k, v, x, gamma)
     cnt = torch.ops.segmentron_hip.segmentation_counts(logits_nchw, target, nclass)
 
@@ -275,6 +277,52 @@ def _uce_bwd(ctx, g):
 
 upsample_cross_entropy.register_autograd(_uce_bwd, setup_context=_uce_setup)
 
+
+# ----------------------------------------------------------------------------- DUpsampling loss
+@torch.library.custom_op(_NS + "::dupsample_cross_entropy", mutates_args=())
+def dupsample_cross_entropy(logits: torch.Tensor, target: torch.Tensor, scale: int, nclass: int,
+                            ignore_index: int) -> torch.Tensor:
+    """F.cross_entropy(DUpsampling(logits), target, ignore_index) (dunet.py:98-117) fused on the
+    low-resolution NHWC output [N, h, w, scale*scale*nclass] of the module's 1x1 convolution.
+    -> float32[2]: (mean loss over the valid pixels, 1 / number of valid pixels)."""
+    return K.dup_ce_fwd(logits, target, scale, nclass, ignore_index)
+
+
+@dupsample_cross_entropy.register_fake
+def _(logits, target, scale, nclass, ignore_index):
+    return logits.new_empty((2,), dtype=torch.float32)
+
+
+@torch.library.custom_op(_NS + "::dupsample_cross_entropy_backward", mutates_args=())
+def dupsample_cross_entropy_backward(logits: torch.Tensor, target: torch.Tensor,
+                                     loss_out: torch.Tensor, grad: torch.Tensor, scale: int,
+                                     nclass: int, ignore_index: int) -> torch.Tensor:
+    k = logits.shape[-1]
+    pitch = _round_up(k, K.vec_of(logits.dtype))
+    d = K.dup_ce_bwd(logits, target, scale, nclass, ignore_index, loss_out, grad, pitch)
+    return d if pitch == k else d[..., :k].contiguous()
+
+
+@dupsample_cross_entropy_backward.register_fake
+def _(logits, target, loss_out, grad, scale, nclass, ignore_index):
+    return logits.new_empty(logits.shape)
+
+
+def _dce_setup(ctx, inputs, output):
+    logits, target, scale, nclass, ignore_index = inputs
+    ctx.save_for_backward(logits, target, output)
+    ctx.cfg = (scale, nclass, ignore_index)
+
+
+def _dce_bwd(ctx, g):
+    logits, target, out = ctx.saved_tensors
+    # only element 0 (the loss) carries gradient
+    return (dupsample_cross_entropy_backward(logits, target, out, g[0].reshape(1).contiguous(),
+                                             *ctx.cfg), None, None, None, None)
+
+
+dupsample_cross_entropy.register_autograd(_dce_bwd, setup_context=_dce_setup)
+
 # ----------------------------------------------------------------------------- criss-cross attention
 @torch.library.custom_op(_NS + "::criss_cross_attention", mutates_args=())
 def criss_cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, x: torch.Tensor,
@@ -344,5 +392,6 @@ def _(logits, target, nclass):
 
 OPS = ("conv2d", "conv2d_backward", "depthwise_conv3x3", "depthwise_conv3x3_backward",
        "interpolate_bilinear", "interpolate_bilinear_backward", "upsample_cross_entropy",
-       "upsample_cross_entropy_backward", "criss_cross_attention",
+       "upsample_cross_entropy_backward", "dupsample_cross_entropy",
+       "dupsample_cross_entropy_backward", "criss_cross_attention",
        "criss_cross_attention_backward", "segmentation_counts")

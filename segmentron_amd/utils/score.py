@@ -38,7 +38,7 @@ class SegmentationMetric(object):
         return self._cnt
 
     def update(self, preds, labels):
-        from ..functional import LogitsView
+        from ..functional import DUpLogitsView, LogitsView
         self._cache = None
         if isinstance(preds, (list, tuple)):
             for p, l in zip(preds, labels):
@@ -50,7 +50,7 @@ class SegmentationMetric(object):
             K.metric_update_upsample(lo, labels, preds.align_corners, self.nclass,
                                      self._counters(lo.device))
             return
-        if isinstance(preds, LogitsView):
+        if isinstance(preds, (LogitsView, DUpLogitsView)):  # (DUNet's view has no pending resize)
             preds = preds.materialize()
         if not isinstance(preds, torch.Tensor) or not preds.is_cuda:
             raise RuntimeError("SegmentationMetric (segmentron_amd) takes HIP device tensors: "
