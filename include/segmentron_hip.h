@@ -31,6 +31,15 @@ extern "C" {
 const char* seg_last_error(void);
 int seg_version(void);
 
+/* The float-reciprocal index division of the grid-stride kernels (csrc/common.h: fast_div), run on
+ * the HOST (no device needed): q[i] = fast_div(s[i], d, 1.f / (float)d) for i < n, returns 0.
+ * seg_fast_div_exact: 1 iff the launchers' guard accepts a largest dividend s with divisor d, i.e.
+ * the division is proven exact for every dividend 0 .. s; seg_fast_div_max_quot: floor(2^24 / 3),
+ * the quotient bound of that guard (as a long through *out). */
+int seg_fast_div_host(const int* s, long n, int d, int* q);
+int seg_fast_div_exact(long s, long d);
+int seg_fast_div_max_quot(long* out);
+
 /* ---- nn.Conv2d, groups=1 (1x1 any stride, dense KxK): implicit GEMM on MFMA ----------------
  * Replaces F.conv2d for segmentron/modules/basic.py:42,69; segmentron/modules/module.py:45,57;
  * segmentron/models/backbones/xception.py:21,77,81; segmentron/models/deeplabv3_plus.py:64.

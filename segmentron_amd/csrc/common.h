@@ -208,6 +208,33 @@ __device__ __forceinline__ int xcd_remap(int b, int nblk) {
   return base + idx;
 }
 
+// q = s / d through a float reciprocal and one fix-up by +-1 (replaces a ~40-instruction integer
+// division in the per-element index decode of the grid-stride kernels).  `inv` is the correctly
+// rounded 1.f / (float)d.  The ONE contract, which fast_div_exact() states as code and every
+// launcher that decodes with fast_div enforces on its largest dividend (tests/test_host_api.py
+// sweeps it on the host through seg_fast_div_host):
+//   0 <= s, 1 <= d, s + d < 2^31 (the fix-up's products stay in int), and
+//   s < 2^24     — (float)s is exact: two roundings (inv, the product) put the estimate within
+//                  2^-23 * s/d < 1 of s/d (d = 1: inv = 1 and the product are exact), or
+//   s / d < FAST_DIV_MAX_QUOT = floor(2^24 / 3) — three roundings ((float)s, inv, the product; a
+//                  fourth, (float)d, only for d >= 2^24, where s/d < 128) of at most 2^-24 each put
+//                  it within (s/d) * 3 * 2^-24 * (1 + 2^-24) < 1 of s/d.
+// An estimate within 1 of s/d truncates to floor(s/d) - 1, floor(s/d) or floor(s/d) + 1, which the
+// fix-up corrects.  Beyond that the result is silently wrong (first at s = 33,554,942, d = 3).
+constexpr long FAST_DIV_MAX_QUOT = (1L << 24) / 3;  // 5,592,405
+
+__host__ __device__ __forceinline__ int fast_div(int s, int d, float inv) {
+  int q = (int)((float)s * inv);
+  if (q * d > s) --q;
+  if ((q + 1) * d <= s) ++q;
+  return q;
+}
+
+// true iff fast_div(s', d, 1.f / (float)d) == s' / d is proven for every 0 <= s' <= s
+inline bool fast_div_exact(long s, long d) {
+  return s >= 0 && d >= 1 && s + d < (1L << 31) && (s < (1L << 24) || s / d < FAST_DIV_MAX_QUOT);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -229,3 +256,12 @@ int check_launch(const char* what);
       return 1;                           \
     }                                     \
   } while (0)
+
+// Guard of a launcher whose kernel decodes element indices 0 .. count*d - 1 with seg::fast_div,
+// first by d (the later divisions have smaller dividends and quotients): see fast_div's contract.
+#define SEG_REQUIRE_FAST_DIV(what, count, d)                                                     \
+  SEG_REQUIRE((long)(count) * (long)(d) == 0 ||                                                  \
+                  seg::fast_div_exact((long)(count) * (long)(d) - 1, (long)(d)),                 \
+              "%s: %ld x %ld indices are beyond the exact range of the float-reciprocal index "  \
+              "division (at most %ld quotients above 2^24 indices, and 2^31 indices)",           \
+              what, (long)(count), (long)(d), seg::FAST_DIV_MAX_QUOT)

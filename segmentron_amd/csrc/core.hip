@@ -1,4 +1,5 @@
-// C-ABI plumbing: error reporting and version for libsegmentron_hip.so.
+// C-ABI plumbing: error reporting and version for libsegmentron_hip.so; the host-side entry
+// points of the index-division helper (common.h: fast_div) that the CPU test sweeps.
 #include "common.h"
 #include <stdarg.h>
 #include <stdio.h>
@@ -25,3 +26,16 @@ int check_launch(const char* what) {
 
 extern "C" const char* seg_last_error(void) { return seg::g_err; }
 extern "C" int seg_version(void) { return 1; }
+
+extern "C" int seg_fast_div_host(const int* s, long n, int d, int* q) {
+  SEG_REQUIRE(s && q && n >= 0 && d >= 1, "fast_div_host: bad arguments");
+  const float inv = 1.f / (float)d;
+  for (long i = 0; i < n; ++i) q[i] = seg::fast_div(s[i], d, inv);
+  return 0;
+}
+extern "C" int seg_fast_div_exact(long s, long d) { return seg::fast_div_exact(s, d) ? 1 : 0; }
+extern "C" int seg_fast_div_max_quot(long* out) {
+  SEG_REQUIRE(out != nullptr, "fast_div_max_quot: null output");
+  *out = seg::FAST_DIV_MAX_QUOT;
+  return 0;
+}

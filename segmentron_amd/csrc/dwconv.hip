@@ -43,14 +43,8 @@ struct DwArgs {
   long strips;        // N * Ho * ceil(Wo / TW)
 };
 
-// q = s / d for 0 <= s < 2^24 via a float reciprocal and one fix-up (replaces a ~40-instruction
-// integer division in the per-strip index decode)
-__device__ __forceinline__ int fast_div(int s, int d, float inv) {
-  int q = (int)((float)s * inv);
-  if (q * d > s) --q;
-  if ((q + 1) * d <= s) ++q;
-  return q;
-}
+// (the per-strip index decode divides with fast_div — common.h states its contract, the launchers
+// below enforce it on the strip count)
 
 template <int VEC>
 __device__ __forceinline__ void dw_act(float* f, int mode, const float* sc, const float* sh) {
@@ -584,7 +578,7 @@ extern "C" int seg_dwconv3x3(int dtype, int mode, const void* x, long ldx, int N
   a.strips = (long)N * Ho * ((Wo + DW_TW - 1) / DW_TW);
   const dim3 grid(strip_gx(a.CV, a.cvb_log2), grid_y);
   const size_t lds = stat_partial ? (size_t)DW_THREADS * 2 * vec * sizeof(float) : 0;
-  SEG_REQUIRE(a.strips < (1L << 31), "dwconv3x3: too many strips");
+  SEG_REQUIRE_FAST_DIV("dwconv3x3", (long)N * Ho, (Wo + DW_TW - 1) / DW_TW);
   SEG_REQUIRE((long)N * Hi * Wi * ldx < (1L << 31), "dwconv3x3: tensor exceeds 32-bit offsets");
 #define SEG_DW_LAUNCH(TT, MM) \
   hipLaunchKernelGGL((dwconv_kernel<TT, MM>), grid, dim3(DW_THREADS), lds, st, a)
@@ -623,7 +617,7 @@ extern "C" int seg_dwconv3x3_wgrad(int dtype, const void* x, long ldx, int N, in
   a.strips = (long)N * Ho * ((Wo + DW_TW - 1) / DW_TW);
   const dim3 grid(strip_gx(a.CV, a.cvb_log2), grid_y);
   const size_t lds = (size_t)DW_THREADS * 3 * vec * sizeof(float);
-  SEG_REQUIRE(a.strips < (1L << 31), "dwconv3x3_wgrad: too many strips");
+  SEG_REQUIRE_FAST_DIV("dwconv3x3_wgrad", (long)N * Ho, (Wo + DW_TW - 1) / DW_TW);
   if (dtype == DT_BF16)
     hipLaunchKernelGGL((dwconv_wgrad_kernel<bf16_t>), grid, dim3(DW_THREADS), lds, st, a);
   else
@@ -683,7 +677,7 @@ static int dw_bwd_fused(const char* name, int dtype, const void* dy, long lddy, 
   a.lddy = lddy; a.ldx = ldx; a.ldg = ldg; a.N = N; a.H = H; a.W = W; a.C = C; a.dil = dil;
   a.pro_mode = pro_mode; a.CV = C / vec;
   a.strips = (long)N * H * ((W + DW_TW - 1) / DW_TW);
-  SEG_REQUIRE(a.strips < (1L << 31), "%s: too many strips", name);
+  SEG_REQUIRE_FAST_DIV(name, (long)N * H, (W + DW_TW - 1) / DW_TW);
   SEG_REQUIRE((long)N * H * W * lddy < (1L << 31), "%s: 32-bit offsets", name);
   const dim3 grid(strip_gx(a.CV, a.cvb_log2), grid_y);
   const size_t lds = (size_t)DW_THREADS * 3 * vec * sizeof(float);

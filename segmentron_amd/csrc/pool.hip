@@ -14,13 +14,6 @@ namespace seg {
 
 constexpr int PL_THREADS = 256;
 
-__device__ __forceinline__ int pl_fast_div(int s, int d, float inv) {
-  int q = (int)((float)s * inv);
-  if (q * d > s) --q;
-  if ((q + 1) * d <= s) ++q;
-  return q;
-}
-
 struct MaxPoolArgs {
   const void* x; void* y; unsigned char* idx;
   const float* scale; const float* shift;
@@ -37,11 +30,11 @@ __global__ __launch_bounds__(PL_THREADS) void maxpool_fwd_kernel(const MaxPoolAr
   const int total = a.N * a.Ho * a.Wo * a.CV;
   const float inv_cv = 1.f / (float)a.CV, inv_wo = 1.f / (float)a.Wo, inv_ho = 1.f / (float)a.Ho;
   for (int i = blockIdx.x * PL_THREADS + threadIdx.x; i < total; i += gridDim.x * PL_THREADS) {
-    int p = pl_fast_div(i, a.CV, inv_cv);
+    int p = fast_div(i, a.CV, inv_cv);
     const int cv = i - p * a.CV;
-    int t = pl_fast_div(p, a.Wo, inv_wo);
+    int t = fast_div(p, a.Wo, inv_wo);
     const int wo = p - t * a.Wo;
-    const int n = pl_fast_div(t, a.Ho, inv_ho);
+    const int n = fast_div(t, a.Ho, inv_ho);
     const int ho = t - n * a.Ho;
     const int c0 = cv * VEC;
     float best[VEC];
@@ -81,11 +74,11 @@ __global__ __launch_bounds__(PL_THREADS) void maxpool_bwd_kernel(const MaxPoolAr
   const int total = a.N * a.Hi * a.Wi * a.CV;
   const float inv_cv = 1.f / (float)a.CV, inv_wi = 1.f / (float)a.Wi, inv_hi = 1.f / (float)a.Hi;
   for (int i = blockIdx.x * PL_THREADS + threadIdx.x; i < total; i += gridDim.x * PL_THREADS) {
-    int p = pl_fast_div(i, a.CV, inv_cv);
+    int p = fast_div(i, a.CV, inv_cv);
     const int cv = i - p * a.CV;
-    int t = pl_fast_div(p, a.Wi, inv_wi);
+    int t = fast_div(p, a.Wi, inv_wi);
     const int w = p - t * a.Wi;
-    const int n = pl_fast_div(t, a.Hi, inv_hi);
+    const int n = fast_div(t, a.Hi, inv_hi);
     const int h = t - n * a.Hi;
     const int c0 = cv * VEC;
     float acc[VEC];
@@ -148,7 +141,7 @@ __global__ __launch_bounds__(PL_THREADS) void adaptive_avgpool_partial_kernel(co
   if (cv < a.CV) {
     const float inv_bw = 1.f / (float)bw;
     for (int q = blockIdx.y * spb + sy; q < npix; q += a.chunks * spb) {
-      const int r = pl_fast_div(q, bw, inv_bw);
+      const int r = fast_div(q, bw, inv_bw);
       const int h = h0 + r, w = w0 + (q - r * bw);
       float f[VEC];
       Vec<T>::unpack(ldg16(X + (((long)n * a.H + h) * a.W + w) * a.ldx + cv * VEC), f);
@@ -177,11 +170,11 @@ __global__ __launch_bounds__(PL_THREADS) void adaptive_avgpool_bwd_kernel(const 
   const int total = a.N * a.H * a.W * a.CV;
   const float inv_cv = 1.f / (float)a.CV, inv_w = 1.f / (float)a.W, inv_h = 1.f / (float)a.H;
   for (int i = blockIdx.x * PL_THREADS + threadIdx.x; i < total; i += gridDim.x * PL_THREADS) {
-    int p = pl_fast_div(i, a.CV, inv_cv);
+    int p = fast_div(i, a.CV, inv_cv);
     const int cv = i - p * a.CV;
-    int t = pl_fast_div(p, a.W, inv_w);
+    int t = fast_div(p, a.W, inv_w);
     const int w = p - t * a.W;
-    const int n = pl_fast_div(t, a.H, inv_h);
+    const int n = fast_div(t, a.H, inv_h);
     const int h = t - n * a.H;
     float acc[VEC];
 #pragma unroll
@@ -234,7 +227,7 @@ extern "C" int seg_maxpool_fwd(int dtype, const void* x, long ldx, int N, int Hi
   SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "maxpool_fwd: bad dtype %d", dtype);
   SEG_REQUIRE(C % vec == 0 && ldx % vec == 0 && ldy % vec == 0, "maxpool_fwd: C/ld multiples of %d", vec);
   SEG_REQUIRE(k >= 1 && k <= 15 && idx != nullptr, "maxpool_fwd: bad kernel size / idx");
-  SEG_REQUIRE((long)N * Ho * Wo * (C / vec) < (1L << 31), "maxpool_fwd: too large");
+  SEG_REQUIRE_FAST_DIV("maxpool_fwd", (long)N * Ho * Wo, C / vec);
   MaxPoolArgs a;
   a.x = x; a.y = y; a.idx = (unsigned char*)idx; a.scale = pro_scale; a.shift = pro_shift;
   a.ldx = ldx; a.ldy = ldy; a.N = N; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.C = C;
@@ -255,7 +248,7 @@ extern "C" int seg_maxpool_bwd(int dtype, void* gx, long ldgx, int N, int Hi, in
   const int vec = dtype == DT_BF16 ? 8 : 4;
   SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "maxpool_bwd: bad dtype %d", dtype);
   SEG_REQUIRE(C % vec == 0 && ldgx % vec == 0 && ldgy % vec == 0, "maxpool_bwd: C/ld multiples of %d", vec);
-  SEG_REQUIRE((long)N * Hi * Wi * (C / vec) < (1L << 31), "maxpool_bwd: too large");
+  SEG_REQUIRE_FAST_DIV("maxpool_bwd", (long)N * Hi * Wi, C / vec);
   MaxPoolArgs a;
   a.x = gx; a.y = const_cast<void*>(gy); a.idx = (unsigned char*)const_cast<void*>(idx);
   a.scale = nullptr; a.shift = nullptr; a.ldx = ldgx; a.ldy = ldgy;
@@ -286,6 +279,9 @@ extern "C" int seg_adaptive_avgpool_partial(int dtype, const void* x, long ldx, 
   SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "adaptive_avgpool: bad dtype %d", dtype);
   SEG_REQUIRE(C % vec == 0 && ldx % vec == 0, "adaptive_avgpool: C/ld multiples of %d", vec);
   SEG_REQUIRE(o >= 1 && o <= H && o <= W && chunks >= 1, "adaptive_avgpool: bad bins/chunks");
+  // (a bin's pixel index is divided by the bin's width: below 2^24 for any width)
+  SEG_REQUIRE((long)H * W <= (1L << 24), "adaptive_avgpool: %d x %d map beyond the 2^24 pixels the "
+              "bin index decode divides exactly", H, W);
   AvgPoolArgs a;
   a.x = x; a.gx = nullptr; a.gy = nullptr; a.partial = partial; a.ldx = ldx; a.ldg = 0; a.ldgy = 0;
   a.N = N; a.H = H; a.W = W; a.C = C; a.CV = C / vec; a.o = o; a.chunks = chunks;
@@ -306,7 +302,7 @@ extern "C" int seg_adaptive_avgpool_bwd(int dtype, void* gx, long ldgx, int N, i
   const int vec = dtype == DT_BF16 ? 8 : 4;
   SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "adaptive_avgpool_bwd: bad dtype %d", dtype);
   SEG_REQUIRE(C % vec == 0 && ldgx % vec == 0 && ldgy % vec == 0, "adaptive_avgpool_bwd: C/ld");
-  SEG_REQUIRE((long)N * H * W * (C / vec) < (1L << 31), "adaptive_avgpool_bwd: too large");
+  SEG_REQUIRE_FAST_DIV("adaptive_avgpool_bwd", (long)N * H * W, C / vec);
   AvgPoolArgs a;
   a.x = nullptr; a.gx = gx; a.gy = gy; a.partial = nullptr; a.ldx = 0; a.ldg = ldgx; a.ldgy = ldgy;
   a.N = N; a.H = H; a.W = W; a.C = C; a.CV = C / vec; a.o = o; a.chunks = 1; a.cvb_log2 = 0;

@@ -427,13 +427,6 @@ struct AddUpArgs {
   int N, H, W, C, CV, mode_x, mode_r, shift, post_relu;
 };
 
-__device__ __forceinline__ int rs_fast_div(int s, int d, float inv) {
-  int q = (int)((float)s * inv);
-  if (q * d > s) --q;
-  if ((q + 1) * d <= s) ++q;
-  return q;
-}
-
 template <typename T>
 __global__ __launch_bounds__(RS_THREADS) void nearest_add_kernel(const AddUpArgs a) {
   constexpr int VEC = Vec<T>::N;
@@ -444,11 +437,11 @@ __global__ __launch_bounds__(RS_THREADS) void nearest_add_kernel(const AddUpArgs
   const int Hr = a.H >> a.shift, Wr = a.W >> a.shift;
   const float inv_cv = 1.f / (float)a.CV, inv_w = 1.f / (float)a.W, inv_h = 1.f / (float)a.H;
   for (int i = blockIdx.x * RS_THREADS + threadIdx.x; i < total; i += gridDim.x * RS_THREADS) {
-    const int p = rs_fast_div(i, a.CV, inv_cv);
+    const int p = fast_div(i, a.CV, inv_cv);
     const int c0 = (i - p * a.CV) * VEC;
-    const int t = rs_fast_div(p, a.W, inv_w);
+    const int t = fast_div(p, a.W, inv_w);
     const int w = p - t * a.W;
-    const int n = rs_fast_div(t, a.H, inv_h);
+    const int n = fast_div(t, a.H, inv_h);
     const int h = t - n * a.H;
     float f[VEC], g[VEC];
     Vec<T>::unpack(ldg16(X + (long)p * a.ldx + c0), f);
@@ -475,11 +468,11 @@ __global__ __launch_bounds__(RS_THREADS) void nearest_sum_bwd_kernel(const AddUp
   const int total = a.N * Hr * Wr * a.CV;
   const float inv_cv = 1.f / (float)a.CV, inv_w = 1.f / (float)Wr, inv_h = 1.f / (float)Hr;
   for (int i = blockIdx.x * RS_THREADS + threadIdx.x; i < total; i += gridDim.x * RS_THREADS) {
-    const int p = rs_fast_div(i, a.CV, inv_cv);
+    const int p = fast_div(i, a.CV, inv_cv);
     const int c0 = (i - p * a.CV) * VEC;
-    const int t = rs_fast_div(p, Wr, inv_w);
+    const int t = fast_div(p, Wr, inv_w);
     const int wr = p - t * Wr;
-    const int n = rs_fast_div(t, Hr, inv_h);
+    const int n = fast_div(t, Hr, inv_h);
     const int hr = t - n * Hr;
     float acc[VEC];
 #pragma unroll
@@ -683,7 +676,7 @@ extern "C" int seg_nearest_add(int dtype, const void* x, long ldx, int mode_x, c
               "nearest_add: C/ld must be multiples of %d", vec);
   SEG_REQUIRE(shift >= 0 && shift < 8 && (H % (1 << shift)) == 0 && (W % (1 << shift)) == 0,
               "nearest_add: H=%d W=%d not divisible by 2^%d", H, W, shift);
-  SEG_REQUIRE((long)N * H * W * (C / vec) < (1L << 31), "nearest_add: too large");
+  SEG_REQUIRE_FAST_DIV("nearest_add", (long)N * H * W, C / vec);
   AddUpArgs a;
   a.x = x; a.r = r; a.y = y; a.sx = sx; a.tx = tx; a.sr = sr; a.tr = tr;
   a.ldx = ldx; a.ldr = ldr; a.ldy = ldy; a.N = N; a.H = H; a.W = W; a.C = C; a.CV = C / vec;
@@ -705,6 +698,8 @@ extern "C" int seg_nearest_sum_bwd(int dtype, const void* g, long ldg, int N, in
   SEG_REQUIRE(C % vec == 0 && ldg % vec == 0 && ldgr % vec == 0, "nearest_sum_bwd: C/ld");
   SEG_REQUIRE(shift >= 0 && shift < 8 && (H % (1 << shift)) == 0 && (W % (1 << shift)) == 0,
               "nearest_sum_bwd: size not divisible");
+  SEG_REQUIRE_FAST_DIV("nearest_sum_bwd", (long)N * (H >> shift) * (W >> shift), C / vec);
+  SEG_REQUIRE((long)N * H * W < (1L << 31), "nearest_sum_bwd: tensor exceeds 32-bit pixel counts");
   AddUpArgs a;
   a.x = g; a.r = nullptr; a.y = gr; a.sx = a.tx = a.sr = a.tr = nullptr;
   a.ldx = ldg; a.ldr = 0; a.ldy = ldgr; a.N = N; a.H = H; a.W = W; a.C = C; a.CV = C / vec;

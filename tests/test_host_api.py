@@ -361,6 +361,91 @@ def test_depthwise_grid_queries_equal_the_recorded_ones_and_refuse_bad_input(gol
         assert q("seg_dwconv3x3_s2_grid_y", *args) == -1
 
 
+FAST_DIV_DIVISORS = (1, 3, 5, 6, 7, 10, 16, 33, 91, 257, 1000)
+# smallest wrong dividends a random search of the float-reciprocal division found, per divisor
+FAST_DIV_KNOWN_WRONG = ((3, 33554942), (5, 67109429), (6, 67109596), (8, 268435605),
+                        (16, 536872553))
+
+
+def test_index_division_helper_is_exact_wherever_the_launchers_accept():
+    """csrc/common.h: fast_div (float reciprocal + one fix-up by +-1) decodes the element index of
+    the pooling, HRNet-fuse and depthwise strip kernels; fast_div_exact is the guard their
+    launchers apply to the largest dividend.  Both run on the host here (seg_fast_div_host,
+    seg_fast_div_exact), the same source the device compiles.
+
+    For every divisor the largest dividend the guard accepts is found FROM THE GUARD (bisection: it
+    is monotone), compared with the documented contract, and the helper is compared with `//` at
+    s = m*d + {-1, 0, 1} for every m of the last 2^18 quotients below that limit, 2^19 evenly
+    spread ones and 2^19 random ones below it, and around 2^24 where (float)s stops being exact:
+    zero mismatches.  The dividends known to divide wrongly must be refused by the guard — and
+    must really come out wrong from the bare helper, so neither half can pass vacuously: a guard
+    widened back to `< 2^31` moves the sweep onto them."""
+    import numpy as np
+    from segmentron_amd import _lib
+    LIB = _lib.LIB
+    out = ctypes.c_long(0)
+    LIB.call("seg_fast_div_max_quot", ctypes.byref(out))
+    QMAX = out.value
+    assert QMAX == (1 << 24) // 3 == 5592405
+
+    def helper(s, d):
+        s = np.ascontiguousarray(s, dtype=np.int32)
+        q = np.full_like(s, -1)
+        LIB.call("seg_fast_div_host", s.ctypes.data, s.size, d, q.ctypes.data)
+        return q
+
+    def accepts(s, d):
+        return LIB.query("seg_fast_div_exact", int(s), int(d)) == 1
+
+    rng = np.random.default_rng(7)
+    checked = 0
+    for d in FAST_DIV_DIVISORS + (8, 4096, (1 << 24) + 1, (1 << 30) - 1):
+        assert accepts(0, d) and not accepts((1 << 31) - d, d) and not accepts(-1, d)
+        lo, hi = 0, (1 << 31) - d  # accepts(lo), not accepts(hi)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if accepts(mid, d) else (lo, mid)
+        smax = lo
+        assert smax == min((1 << 31) - d - 1, max((1 << 24) - 1, QMAX * d - 1)), (d, smax)
+        mmax = smax // d
+        ms = [np.arange(max(0, mmax - (1 << 18)), mmax + 2, dtype=np.int64),
+              np.linspace(0, mmax, 1 << 19).astype(np.int64),
+              rng.integers(0, mmax + 1, 1 << 19),
+              np.arange(max(0, (1 << 24) // d - 4096), min(mmax, (1 << 24) // d + 4096) + 1,
+                        dtype=np.int64)]
+        m = np.unique(np.concatenate(ms))
+        s = (m[:, None] * d + np.array([-1, 0, 1])[None, :]).ravel()
+        s = np.concatenate([s, np.arange(max(0, smax - 4096), smax + 1, dtype=np.int64)])
+        s = s[(s >= 0) & (s <= smax)]
+        assert s.max() == smax
+        bad = np.flatnonzero(helper(s, d) != s // d)
+        assert bad.size == 0, "d = %d: %d wrong quotients inside the guard, first at s = %d" % (
+            d, bad.size, s[bad[0]])
+        checked += s.size
+    assert checked > 20e6
+    for d, s in FAST_DIV_KNOWN_WRONG:
+        assert not accepts(s, d), (s, d)
+        assert helper([s], d)[0] != s // d, "the bare helper is expected to be wrong at %d / %d" % (s, d)
+    # the guard in the launchers themselves: refused before any launch (no device is touched)
+    dummy = np.zeros(64, dtype=np.float32).ctypes.data
+    F32 = 0
+    big = 2400  # 2400 x 2400 = 5.76 M pixels > QMAX, times 4 vectors of C = 16: above 2^24 indices
+    refused = [
+        ("seg_maxpool_fwd", (F32, dummy, 16, 1, 2 * big, 2 * big, 16, 3, 2, 1, 0, 0, 0, dummy, 16,
+                             big, big, dummy, 0)),
+        ("seg_maxpool_bwd", (F32, dummy, 16, 1, big, big, 16, 3, 2, 1, dummy, 16, big // 2, big // 2,
+                             dummy, 0)),
+        ("seg_adaptive_avgpool_bwd", (F32, dummy, 16, 1, big, big, 16, 2, dummy, 16, 0)),
+        ("seg_adaptive_avgpool_partial", (F32, dummy, 16, 1, 4097, 4096, 16, 1, dummy, 4, 0)),
+        ("seg_nearest_add", (F32, dummy, 16, 0, 0, 0, dummy, 16, 0, 0, 0, 1, 0, dummy, 16, 1, big,
+                             big, 16, 0)),
+        ("seg_nearest_sum_bwd", (F32, dummy, 16, 1, big, big, 16, 0, dummy, 16, 0)),
+    ]
+    for name, args in refused:
+        with pytest.raises(RuntimeError, match="float-reciprocal index|divides exactly"):
+            LIB.call(name, *args)
+
+
 def test_frozen_batchnorm_module_contract():
     """get_norm('FrozenBN') — segmentron/modules/batch_norm.py:10-104,107-132: four BUFFERS, the
     reference's state_dict keys, its version-3 loading rule, convert_frozen_batchnorm; 'GN'

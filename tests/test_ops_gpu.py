@@ -717,6 +717,21 @@ def test_errors_are_reported_not_fatal():
         K().conv_gemm(x, w, 8, 1, 1, 1, 0, 1)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         K().bn_apply(torch.zeros(1, 2, 2, 8))
+    # sizes beyond what the float-reciprocal index division of the grid-stride kernels divides
+    # exactly (csrc/common.h: fast_div; 2400 x 2400 = 5.76 M pixels x 4 vectors) are refused
+    # before any launch: the tensors are dummies
+    from segmentron_amd._lib import LIB
+    d, big = torch.zeros(64, device=DEV).data_ptr(), 2400
+    for name, args in (
+            ("seg_maxpool_fwd", (0, d, 16, 1, 2 * big, 2 * big, 16, 3, 2, 1, 0, 0, 0, d, 16, big, big, d, 0)),
+            ("seg_maxpool_bwd", (0, d, 16, 1, big, big, 16, 3, 2, 1, d, 16, big // 2, big // 2, d, 0)),
+            ("seg_adaptive_avgpool_bwd", (0, d, 16, 1, big, big, 16, 2, d, 16, 0)),
+            ("seg_adaptive_avgpool_partial", (0, d, 16, 1, 4097, 4096, 16, 1, d, 4, 0)),
+            ("seg_nearest_add", (0, d, 16, 0, 0, 0, d, 16, 0, 0, 0, 1, 0, d, 16, 1, big, big, 16, 0)),
+            ("seg_nearest_sum_bwd", (0, d, 16, 1, big, big, 16, 0, d, 16, 0))):
+        with pytest.raises(RuntimeError, match="float-reciprocal index|divides exactly"):
+            LIB.call(name, *args)
+    torch.cuda.synchronize()  # (nothing was launched, nothing faulted)
 
 
 # ------------------------------------------------------------------------------ BN fold
