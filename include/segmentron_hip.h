@@ -378,6 +378,33 @@ int seg_chan_gate_bwd_finalize(const float* partial, int chunks, int N, int C, c
 int seg_bcast_add(int dtype, const void* g, long ldg, const float* v, float scale, void* y,
                   long ldy, int N, long HW, int C, int chunks, void* stream);
 
+/* ---- CGNet's ContextGuidedBlock (csrc/cgnet.hip; segmentron/models/cgnet.py:149-181) -----------
+ * NHWC; partial rows are fp32, one per (pixel chunk, image), summed in index order: no atomics,
+ * bit-identical results on every launch, and no image reaches another image's rows.
+ *   seg_cg_joint_fwd   y[..., :C] = depthwise 3x3 (w_loc, pad 1) of x, y[..., C:2C] = depthwise 3x3
+ *                      (w_sur, pad = dilation = dil) of the same x, one pass; w_loc / w_sur are the
+ *                      [C,1,3,3] parameters as they are; C % 4 == 0, pitches % 4 == 0;
+ *                      partial[chunks * N][2][2C] (nullable) = sum | sum of squares of the fp32
+ *                      accumulators, chunks = seg_cg_joint_chunks(N, H, W, C) (or any 1..256)
+ *   seg_bn_prelu_fwd   y = prelu(x * scale[c] + shift[c], alpha[c]) (scale / shift both null: plain
+ *                      PReLU; y nullable: sums only) and partial[chunks][N][C] (nullable) = per-image
+ *                      sums of the fp32 activated values, chunks as seg_apply_pool_chunks.  Any
+ *                      C >= 1: every pitch holds C rounded up to 8, the parameter arrays have
+ *                      exactly C elements, and y's channels [C, round_up(C, 8)) are written as zeros
+ *   seg_prelu_bwd      g = g_y + g_pool[n][c] / HW (either nullable), z = x * scale + shift,
+ *                      g_z = z > 0 ? g : alpha * g (pad channels: zeros), partial[chunks][N][C] =
+ *                      sum over z <= 0 of g * z: dalpha = seg_colsum over the chunks * N rows */
+int seg_cg_joint_chunks(int N, int H, int W, int C);
+int seg_cg_joint_fwd(int dtype, const void* x, long ldx, int N, int H, int W, int C,
+                     const float* w_loc, const float* w_sur, int dil, void* y, long ldy,
+                     float* partial, int chunks, void* stream);
+int seg_bn_prelu_fwd(int dtype, const void* x, long ldx, const float* scale, const float* shift,
+                     const float* alpha, void* y, long ldy, int N, long HW, int C, float* partial,
+                     int chunks, void* stream);
+int seg_prelu_bwd(int dtype, const void* g_y, long ldgy, const float* g_pool, const void* x,
+                  long ldx, const float* scale, const float* shift, const float* alpha, void* g_z,
+                  long ldgz, int N, long HW, int C, float* partial, int chunks, void* stream);
+
 /* ---- F.interpolate(mode='bilinear') ---------------------------------------------------------
  * Replaces segmentron/models/deeplabv3_plus.py:39,44,71; segmentron/modules/module.py:64,96;
  * segmentron/models/segbase.py:83.  NHWC -> NHWC with optional prologue and per-(n,c) multiplier. */

@@ -603,16 +603,21 @@ class _ConvFn(torch.autograd.Function):
         dx = dgamma = dbeta = None
         if ctx.needs_input_grad[0]:
             Op, dt = dy_full.shape[-1], x.dtype
-            if KH == 1 and KW == 1 and Op == O and weight.dtype == torch.float32:
+
+            def rows(w2d):
+                # the input is a channel-padded buffer (CGNet's 35-channel concat in 40: Cx > Cw):
+                # zero rows, so that the data gradient has the input's width, zeros in its pads
+                return w2d if Cx == Cw else torch.nn.functional.pad(w2d, (0, 0, 0, Cx - Cw))
+            if KH == 1 and KW == 1 and Op == O and Cx == Cw and weight.dtype == torch.float32:
                 wt = packed_pointwise(weight, True, dt)
             else:
-                wt = cached_pack(weight, ("dgrad", Op, dt),
-                                 lambda: pack_conv_weight_dgrad(weight, Op, dt))
+                wt = cached_pack(weight, ("dgrad", Op, dt, Cx),
+                                 lambda: rows(pack_conv_weight_dgrad(weight, Op, dt)))
             res = None
             if s.fork is not None and s.fork.g is not None:
                 res = s.fork.take()  # the identity path's gradient of a forked block input
             if s.stride == 1 and res is not None and KH == 1 and KW == 1 and s.bn_in is None \
-                    and not s.relu and Cw % K.vec_of(dt) == 0 and res.dtype == dt:
+                    and not s.relu and Cx == Cw and Cw % K.vec_of(dt) == 0 and res.dtype == dt:
                 # ... rides in the data-gradient GEMM's store path: the epilogue's
                 # y = acc - c0 - c1 * x with c0 = 0, c1 = -1 (ResNet bottlenecks, resnet.py:52-79:
                 # 33 element-wise adds of 135 MB tensors per PSPNet step, 2.4 of 72 ms)
@@ -620,14 +625,14 @@ class _ConvFn(torch.autograd.Function):
                                    ep=(res, _const(Cw, x.device, 0.0), _const(Cw, x.device, -1.0)))
                 res = None
             elif s.stride == 1:
-                g, _ = K.conv_gemm(dy_full, wt, Cw, KH, KW, 1, s.dil * (KH - 1) - s.pad, s.dil)
+                g, _ = K.conv_gemm(dy_full, wt, Cx, KH, KW, 1, s.dil * (KH - 1) - s.pad, s.dil)
             elif KH == 1 and KW == 1 and s.pad == 0:
-                g, _ = K.conv_gemm(dy_full, wt, Cw, 1, 1, 1, 0, 1,
+                g, _ = K.conv_gemm(dy_full, wt, Cx, 1, 1, 1, 0, 1,
                                    scatter=(x.shape[1], x.shape[2], s.stride))
             else:  # strided KxK: transposed-stride gather through the same MFMA kernel
-                wt = cached_pack(weight, ("tconv", Op, dt),
-                                 lambda: pack_conv_weight_tconv(weight, Op, dt))
-                g, _ = K.conv_gemm(dy_full, wt, Cw, KH, KW, s.stride, s.pad, s.dil,
+                wt = cached_pack(weight, ("tconv", Op, dt, Cx),
+                                 lambda: rows(pack_conv_weight_tconv(weight, Op, dt)))
+                g, _ = K.conv_gemm(dy_full, wt, Cx, KH, KW, s.stride, s.pad, s.dil,
                                    tconv_out_hw=(x.shape[1], x.shape[2]))
             p = s.park
             if res is None and p is not None and p.kind in (GradFork.SUM, GradFork.PRE) \
@@ -1286,13 +1291,13 @@ class _ChanGateFn(torch.autograd.Function):
     last_feature`, bisenet.py:159-161).  x, r plain NHWC; a, radd float32 [N,1,1,C]."""
 
     @staticmethod
-    def forward(ctx, x, a, r, radd, identity):
+    def forward(ctx, x, a, r, radd, identity, out=None):
         N, H, W, C = x.shape
         a2 = a.detach().reshape(N, C).contiguous()
         radd2 = None if radd is None else radd.detach().reshape(N, C).contiguous()
         ctx.identity = identity
         ctx.save_for_backward(x, a2)
-        return K.chan_gate(x, a2, identity, r, radd2)
+        return K.chan_gate(x, a2, identity, r, radd2, out)  # (`out`: a slice of a concat buffer)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1307,7 +1312,7 @@ class _ChanGateFn(torch.autograd.Function):
             da = da.view(N, 1, 1, C)
         if dradd is not None:
             dradd = dradd.view(N, 1, 1, C)
-        return dx, da, (dy if need[2] else None), dradd, None  # (d/dr is dy itself: no copy)
+        return dx, da, (dy if need[2] else None), dradd, None, None  # (d/dr is dy itself)
 
 
 class PoolSpec:
@@ -1845,6 +1850,205 @@ def channel_gate(act, branch, identity=False, residual=None, bcast_residual=None
         if radd.dtype != torch.float32:
             radd = radd.float()
     return _ChanGateFn.apply(y, a, residual, radd, bool(identity))
+
+
+def gate(x, a, identity=False, residual=None, out=None):
+    """x * (identity + sigmoid(a)) + residual on plain NHWC tensors (a: float32 [N,1,1,C], the
+    pre-sigmoid output of the attention branch) — channel_gate's last step alone, for a caller
+    that pooled x itself (CGNet's _FGlo: cgnet.py:106-120 plus the block's `out + x`).  `out`: a
+    channel slice of a concat buffer."""
+    if a.dtype != torch.float32:
+        a = a.float()
+    return _ChanGateFn.apply(x, a, residual, None, bool(identity), out)
+
+
+# ---- CGNet: BatchNorm + PReLU write-out, joint local / surround depthwise (csrc/cgnet.hip) ------
+def _pad_bn(bn, Cp):
+    """The BNState of a ragged channel count (35, 131) padded with zeros to the buffer's width,
+    for the BatchNorm-backward kernels, which work on whole channel vectors: in the pad channels
+    x = g = gamma = 0, so their dx, dgamma and dbeta are exact zeros."""
+    C = bn.scale.numel()
+    if C == Cp:
+        return bn
+
+    def pad(t):
+        return None if t is None else torch.nn.functional.pad(t, (0, Cp - C))
+    return BNState(pad(bn.gamma), pad(bn.beta), pad(bn.mean), pad(bn.invstd), pad(bn.scale),
+                   pad(bn.shift), bn.count, bn.training, bn.group)
+
+
+class BNPReLUSpec:
+    def __init__(self, act, pool, out):
+        self.bn, self.pool, self.out = act.bn, pool, out
+
+
+class _BNPReLUFn(torch.autograd.Function):
+    """y = prelu(bn(x), alpha) written out once (+ nn.AdaptiveAvgPool2d(1) of it from the same
+    pass): `_ConvBNPReLU` / `_BNPReLU` of segmentron/modules/basic.py and the `prelu(bn(joi))` of
+    the ContextGuidedBlock.  Backward: the PReLU mask and dalpha by seg_prelu_bwd on the recomputed
+    z, then the one BatchNorm backward every other consumer uses (bn_input_backward, relu=False)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, alpha, spec):
+        N, H, W, _ = x.shape
+        C = alpha.numel()
+        bn = spec.bn
+        al = alpha.detach().float().contiguous()
+        y, sums = K.bn_prelu(x, al, None if bn is None else bn.scale,
+                             None if bn is None else bn.shift, pool=spec.pool, out=spec.out)
+        spec.out = None  # (it IS y: kept, ctx -> spec -> y -> grad_fn -> ctx would be a cycle)
+        ctx.spec = spec
+        ctx.save_for_backward(x, al)
+        if not spec.pool:
+            return y
+        return y, (sums / float(H * W)).view(N, 1, 1, C)
+
+    @staticmethod
+    def backward(ctx, g_y, g_p=None):
+        x, al = ctx.saved_tensors
+        bn = ctx.spec.bn
+        N, H, W, Cx = x.shape
+        C = al.numel()
+        if g_y is None and g_p is None:
+            return None, None, None, None, None
+        if g_y is not None and (g_y.dtype != x.dtype or not _sum_n_operand_ok(g_y, K.vec_of(x.dtype))
+                                or K.nhwc(g_y)[4] < K.round_up8(C)):
+            g_y = g_y.to(x.dtype).contiguous()
+            if g_y.shape[-1] != K.round_up8(C):
+                g_y = torch.nn.functional.pad(g_y, (0, K.round_up8(C) - g_y.shape[-1]))
+        v = None if g_p is None else g_p.reshape(N, C).float().contiguous()
+        g_z, dalpha = K.prelu_bwd(g_y, v, x, al, None if bn is None else bn.scale,
+                                  None if bn is None else bn.shift)
+        dgamma = dbeta = None
+        if bn is None:
+            dx = g_z
+        else:
+            xp = x if Cx == g_z.shape[-1] else x.as_strided(g_z.shape, x.stride(),
+                                                            x.storage_offset())
+            dx, dgamma, dbeta = bn_input_backward(g_z, xp, _pad_bn(bn, g_z.shape[-1]), False,
+                                                  inplace=True)
+            if dgamma is not None:
+                dgamma, dbeta = dgamma[:C], dbeta[:C]
+        if dx.shape[-1] != Cx:
+            dx = dx[..., :Cx]
+        return (dx if ctx.needs_input_grad[0] else None), dgamma, dbeta, dalpha, None
+
+
+def bn_prelu(act, prelu, pool=False, out=None):
+    """-> plain NHWC tensor prelu(act) (act: an Act whose BatchNorm is pending, or a plain one;
+    prelu: nn.PReLU with one slope per channel), with `pool` also its nn.AdaptiveAvgPool2d(1) as
+    float32 [N,1,1,C] from the same pass.  PReLU is never a pending prologue: its output is
+    materialised here.  A ragged channel count (CGNet's 35 and 131) lives in a buffer of
+    round_up8(C) channels: act.t has that width with zeros beyond C, and so has the result."""
+    if act.relu:
+        raise ValueError("bn_prelu: the activation already carries a pending ReLU")
+    if prelu.weight.numel() == 1 and act.t.shape[-1] != 1:
+        raise NotImplementedError("bn_prelu: nn.PReLU(1) (one shared slope) is not on the HIP path")
+    g, b = act.params
+    return _BNPReLUFn.apply(act.t, g, b, prelu.weight, BNPReLUSpec(act, pool, out))
+
+
+def bn_of_concat(buf, bn, C=None):
+    """The BatchNorm of an already materialised tensor (CGNet's bn_prelu1/2/3 over the stage
+    concats) -> Act(buf, pending BatchNorm).  buf: plain NHWC, C (default: all) valid channels in
+    a buffer of round_up8(C) whose pad channels are zero.  The statistics are one pass of the
+    existing moments reduction (hip_ops.chan_moments) at the buffer's width."""
+    N, H, W, Cb = buf.shape
+    C = Cb if C is None else C
+    partial = None
+    if uses_batch_stats(bn):
+        partial = K.chan_moments(buf)
+        if C != Cb:
+            partial = partial[:, :, :C].contiguous()
+    y = buf if C == Cb else buf[..., :C]
+    return Act(buf, finish_bn(bn, partial, N * H * W, y=y))
+
+
+def cg_joint_routed(dtype, C, dil):
+    """Does the FORWARD of cg_joint_bn run on the joint kernel (csrc/cgnet.hip) rather than on the
+    two depthwise launches it replaces?  Measured at CGNet's two workload shapes
+    (profiles/cgnet.md, tools/cgnet_bench.py): at dilation 4 ([4,96,96,64], the 21 blocks at 1/8
+    resolution) the joint kernel takes 0.37 x the time of the pair in bf16 and 0.38 x in fp32; at
+    dilation 2 ([4,192,192,32]) it ties in bf16 and loses in fp32 against the sliding + LDS-tiled
+    pair.  The dividing line is the surround branch's kernel family: beyond dilation 2 it is the
+    row-chain family, which the joint kernel beats."""
+    return dil > 2 and C % 4 == 0
+
+
+class CGJointSpec:
+    def __init__(self, dil, want_stats, joint):
+        self.dil, self.want_stats, self.joint, self.partial = dil, want_stats, joint, None
+
+
+def _cat_partials(p1, p2):
+    """Statistic partial rows [R1, 2, C] and [R2, 2, C] of the two halves of a channel concat ->
+    [max(R1, R2), 2, 2C] (missing rows are zeros: the rows are only ever summed)."""
+    if p1.shape[0] == p2.shape[0]:
+        return torch.cat([p1, p2], 2)
+    C = p1.shape[2]
+    out = torch.zeros((max(p1.shape[0], p2.shape[0]), 2, 2 * C), dtype=p1.dtype, device=p1.device)
+    out[:p1.shape[0], :, :C] = p1
+    out[:p2.shape[0], :, C:] = p2
+    return out
+
+
+class _CGJointFn(torch.autograd.Function):
+    """cat([f_loc(x), f_sur(x)], 1) of the ContextGuidedBlock (cgnet.py:169-172) with the BatchNorm
+    statistics of the concat from the convolutions' own accumulators.  Forward: the joint kernel
+    (one pass over x) where cg_joint_routed, else the two depthwise launches, each into its channel
+    slice.  Backward: the two fused depthwise backward launches (data gradient + weight-gradient
+    rows each); the surround branch's data gradient rides in the store path of the local one, so
+    no separate sum pass runs."""
+
+    @staticmethod
+    def forward(ctx, x, w_loc, w_sur, spec):
+        N, H, W, C = x.shape
+        d = spec.dil
+        if spec.joint:
+            y, spec.partial = K.cg_joint(x, w_loc.detach().contiguous(),
+                                         w_sur.detach().contiguous(), d,
+                                         want_stats=spec.want_stats)
+        else:
+            y = torch.empty((N, H, W, 2 * C), dtype=x.dtype, device=x.device)
+            _, p1 = K.dwconv(x, _dw_taps(w_loc, 1, 1), 1, 1, None, y[..., :C], spec.want_stats)
+            _, p2 = K.dwconv(x, _dw_taps(w_sur, 1, d), 1, d, None, y[..., C:], spec.want_stats)
+            spec.partial = _cat_partials(p1, p2) if spec.want_stats else None
+        ctx.dil = d
+        ctx.save_for_backward(x, w_loc, w_sur)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w_loc, w_sur = ctx.saved_tensors
+        C, d = x.shape[-1], ctx.dil
+        if g.dtype != x.dtype or not _sum_n_operand_ok(g, K.vec_of(x.dtype)):
+            g = g.to(x.dtype).contiguous()
+        tiled = K.dw_tiled(1, d)
+        g_sur, dws, _ = K.dwconv_bwd_fused(x, g[..., C:], _dw_taps(w_sur, 1, d), d, None,
+                                           torch_layout=tiled)
+        if not tiled:
+            dws = K.dw_torch_layout(dws)
+        if K.dwconv_bwd_fused_add_ok(1) and C % 4 == 0:
+            dx, dwl, _ = K.dwconv_bwd_fused(x, g[..., :C], _dw_taps(w_loc, 1, 1), 1, None,
+                                            torch_layout=True, res=g_sur)
+        else:
+            g_loc, dwl, _ = K.dwconv_bwd_fused(x, g[..., :C], _dw_taps(w_loc, 1, 1), 1, None,
+                                               torch_layout=True)
+            dx = K.sum_n([g_loc, g_sur])
+        return dx, dwl, dws, None
+
+
+def cg_joint_bn(t, f_loc, f_sur, bn):
+    """t: plain NHWC tensor; f_loc / f_sur: the two nn.Conv2d(C, C, 3, groups=C) of a
+    ContextGuidedBlock (dilation 1 and d); bn: the BatchNorm over their concat.  -> Act([N,H,W,2C],
+    BatchNorm pending)."""
+    N, H, W, C = t.shape
+    d = f_sur.dilation[0]
+    assert f_loc.dilation[0] == 1 and f_loc.padding[0] == 1 and f_sur.padding[0] == d
+    assert f_loc.stride[0] == 1 and f_sur.stride[0] == 1 and f_loc.groups == C == f_sur.groups
+    spec = CGJointSpec(d, uses_batch_stats(bn), cg_joint_routed(t.dtype, C, d))
+    y = _CGJointFn.apply(t, f_loc.weight, f_sur.weight, spec)
+    return Act(y, finish_bn(bn, spec.partial, N * H * W, y=y))
 
 
 def max_pool(act, k, stride, pad):

@@ -850,6 +850,140 @@ def bcast_add(g, v, scale, like=None, inplace=True):
     return out
 
 
+# ---- CGNet's ContextGuidedBlock (csrc/cgnet.hip) -------------------------------------------------
+def round_up8(C):
+    """Channel width of a buffer that holds C channels for the kernels of csrc/cgnet.hip."""
+    return (C + 7) // 8 * 8
+
+
+def _padded_view(t, N, H, W, C, what, dtype=None):
+    """-> the row pitch of `t`, an NHWC view of C (or C rounded up to 8) channels whose rows hold C
+    rounded up to 8 elements — the element-wise kernels of csrc/cgnet.hip read and write whole
+    channel vectors up to there."""
+    n, h, w, c, ld = nhwc(t)
+    Cp = round_up8(C)
+    if (n, h, w) != (N, H, W) or c not in (C, Cp) or (dtype is not None and t.dtype != dtype):
+        raise RuntimeError("%s: expected %s %s (or %d channels), got %s %s"
+                           % (what, (N, H, W, C), dtype, Cp, tuple(t.shape), t.dtype))
+    if n * h * w == 1 and c < Cp:
+        # (a single row has no pitch that could show the room behind its C channels)
+        raise RuntimeError("%s: a single-row tensor of a ragged channel count is passed as the "
+                           "view of all %d channels of its buffer, got %d" % (what, Cp, c))
+    if ld < Cp or ld % vec_of(t.dtype) != 0:
+        raise RuntimeError("%s: row pitch %d does not hold %d channels in whole %d-element vectors"
+                           % (what, ld, Cp, vec_of(t.dtype)))
+    return ld
+
+
+def _chan_param(t, C, what):
+    if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                              and t.numel() == C):
+        raise RuntimeError("%s: expected a contiguous float32 device tensor of %d elements"
+                           % (what, C))
+    return t
+
+
+def bn_prelu(x, alpha, scale=None, shift=None, want_y=True, pool=False, out=None):
+    """-> (y | None, sums fp32 [N, C] | None): y = prelu(x * scale + shift, alpha) (scale / shift
+    None: plain PReLU) and, with `pool`, the per-image sums of the fp32 activated values, in one
+    pass.  C = alpha.numel() may be ragged (35, 131): x and y are views of C or round_up8(C)
+    channels whose row pitch holds round_up8(C); y is allocated at round_up8(C) channels and its
+    channels beyond C are written as zeros; the parameter arrays have exactly C elements."""
+    C = alpha.numel()
+    N, H, W = x.shape[0], x.shape[1], x.shape[2]
+    ldx = _padded_view(x, N, H, W, C, "bn_prelu x")
+    _chan_param(alpha, C, "bn_prelu alpha")
+    _chan_param(scale, C, "bn_prelu scale")
+    _chan_param(shift, C, "bn_prelu shift")
+    if (scale is None) != (shift is None):
+        raise RuntimeError("bn_prelu: scale and shift go together")
+    if not (want_y or pool):
+        raise RuntimeError("bn_prelu: neither y nor the pooled sums wanted")
+    y, ldy = None, 0
+    if want_y:
+        y = out if out is not None else \
+            torch.empty((N, H, W, round_up8(C)), dtype=x.dtype, device=x.device)
+        ldy = _padded_view(y, N, H, W, C, "bn_prelu out", x.dtype)
+    chunks = _gate_chunks(N, H * W, C)
+    partial = torch.empty((chunks, N * C), dtype=torch.float32, device=x.device) if pool else None
+    LIB.call("seg_bn_prelu_fwd", _DT[x.dtype], _p(x), ldx, _p(scale), _p(shift), _p(alpha), _p(y),
+             ldy, N, H * W, C, _p(partial), chunks, _stream())
+    sums = None
+    if pool:
+        sums = (partial[0] if chunks == 1 else colsum(partial, f64=False)).view(N, C)
+    return y, sums
+
+
+def prelu_bwd(g_y, g_pool, x, alpha, scale=None, shift=None, out=None):
+    """PReLU backward behind bn_prelu -> (g_z, dalpha fp32 [C]): g = g_y + g_pool[n][c] / HW
+    (either may be None), z = x * scale + shift recomputed, g_z = z > 0 ? g : alpha * g (the slope
+    at z == 0 is alpha, as torch), dalpha = sum over z <= 0 of g * z.  g_z has round_up8(C)
+    channels, zeros beyond C: it goes to bn_bwd_* / the producer at that width."""
+    C = alpha.numel()
+    N, H, W = x.shape[0], x.shape[1], x.shape[2]
+    ldx = _padded_view(x, N, H, W, C, "prelu_bwd x")
+    _chan_param(alpha, C, "prelu_bwd alpha")
+    _chan_param(scale, C, "prelu_bwd scale")
+    _chan_param(shift, C, "prelu_bwd shift")
+    if (scale is None) != (shift is None):
+        raise RuntimeError("prelu_bwd: scale and shift go together")
+    if g_y is None and g_pool is None:
+        raise RuntimeError("prelu_bwd: no gradient at all")
+    ldgy = 0 if g_y is None else _padded_view(g_y, N, H, W, C, "prelu_bwd g_y", x.dtype)
+    _nc(g_pool, N, C, "prelu_bwd g_pool")
+    g_z = out if out is not None else \
+        torch.empty((N, H, W, round_up8(C)), dtype=x.dtype, device=x.device)
+    ldgz = _padded_view(g_z, N, H, W, C, "prelu_bwd out", x.dtype)
+    chunks = _gate_chunks(N, H * W, C)
+    partial = torch.empty((chunks * N, C), dtype=torch.float32, device=x.device)
+    LIB.call("seg_prelu_bwd", _DT[x.dtype], _p(g_y), ldgy, _p(g_pool), _p(x), ldx, _p(scale),
+             _p(shift), _p(alpha), _p(g_z), ldgz, N, H * W, C, _p(partial), chunks, _stream())
+    return g_z, colsum(partial, f64=False)
+
+
+def _cg_weights(w_loc, w_sur, C):
+    for w in (w_loc, w_sur):
+        if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
+                and tuple(w.shape) == (C, 1, 3, 3)):
+            raise RuntimeError("cg_joint: the weights are contiguous float32 [%d,1,3,3] device "
+                               "tensors, got %s %s" % (C, tuple(w.shape), w.dtype))
+
+
+def _cg_chunks(N, H, W, C):
+    chunks = LIB.query("seg_cg_joint_chunks", N, H, W, C)
+    if chunks < 1:
+        raise ValueError("seg_cg_joint_chunks(%d, %d, %d, %d): empty tensor, or C is not a "
+                         "multiple of 4" % (N, H, W, C))
+    return chunks
+
+
+def cg_joint(x, w_loc, w_sur, dil, out=None, want_stats=True):
+    """-> (joi [N,H,W,2C], partial fp32 [rows, 2, 2C] | None): joi[..., :C] = depthwise 3x3 of x
+    with w_loc (pad 1), joi[..., C:] = depthwise 3x3 with w_sur (pad = dilation = dil), one pass
+    over x; partial: sum | sum of squares of the fp32 accumulators for finish_bn."""
+    N, H, W, C, ldx = nhwc(x)
+    _cg_weights(w_loc, w_sur, C)
+    if out is None:
+        out = torch.empty((N, H, W, 2 * C), dtype=x.dtype, device=x.device)
+    if tuple(out.shape) != (N, H, W, 2 * C) or out.dtype != x.dtype:
+        raise RuntimeError("cg_joint out: expected %s %s, got %s %s"
+                           % ((N, H, W, 2 * C), x.dtype, tuple(out.shape), out.dtype))
+    chunks = _cg_chunks(N, H, W, C)
+    partial = torch.empty((chunks * N, 2, 2 * C), dtype=torch.float32, device=x.device) \
+        if want_stats else None
+    LIB.call("seg_cg_joint_fwd", _DT[x.dtype], _p(x), ldx, N, H, W, C, _p(w_loc), _p(w_sur),
+             int(dil), _p(out), nhwc(out)[4], _p(partial), chunks, _stream())
+    return out, partial
+
+
+def chan_moments(x):
+    """Per-channel (sum, sum of squares) partial rows fp32 [R, 2, C] of a plain pitched NHWC tensor
+    for finish_bn — the existing seg_bn_bwd_reduce with g = x and no prologue (column sums of
+    (x, x*x), as functional._GapFn uses it)."""
+    C = x.shape[-1]
+    return bn_bwd_reduce_partial(x, x, None).view(-1, 2, C)
+
+
 _BIN_AREAS = {}
 
 

@@ -10,3 +10,4 @@ from .danet import DANet  # noqa: F401
 from .pointrend import PointRend  # noqa: F401
 from .bisenet import BiSeNet  # noqa: F401
 from .dunet import DUNet  # noqa: F401
+from .cgnet import CGNet  # noqa: F401

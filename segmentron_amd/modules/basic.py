@@ -7,7 +7,8 @@ import torch.nn as nn
 
 from .. import functional as F
 
-__all__ = ["SeparableConv2d", "_ConvBNReLU", "InvertedResidual"]
+__all__ = ["SeparableConv2d", "_ConvBNReLU", "_ConvBNPReLU", "_ConvBN", "_BNPReLU",
+           "InvertedResidual"]
 
 
 class SeparableConv2d(nn.Module):
@@ -72,6 +73,58 @@ class _ConvBNReLU(nn.Module):
             a = F.conv_bn(act, self.conv, self.bn, out=out)
         a.relu = F.RELU6 if self.relu6 else F.RELU
         return a
+
+
+class _ConvBNPReLU(nn.Module):
+    """conv (groups=1) -> BN -> PReLU (basic.py:80-92).  PReLU is not a prologue the consumers
+    can apply: the activation is written out once (functional.bn_prelu); returns the plain NHWC
+    tensor, with `pool` also its global average [N,1,1,C] float32 from the same pass."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
+                 groups=1, norm_layer=nn.BatchNorm2d):
+        super().__init__()
+        if groups != 1:
+            raise NotImplementedError("only dense convolutions are on the HIP path here")
+        self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, dilation,
+                              groups, bias=False)
+        self.bn = norm_layer(out_channels)
+        self.prelu = nn.PReLU(out_channels)
+
+    def forward(self, act, pool=False, out=None):
+        return F.bn_prelu(F.conv_bn(act, self.conv, self.bn), self.prelu, pool=pool, out=out)
+
+
+class _ConvBN(nn.Module):
+    """conv (groups=1 or depthwise 3x3) -> BN (basic.py:95-105); returns a deferred activation."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
+                 groups=1, norm_layer=nn.BatchNorm2d, **kwargs):
+        super().__init__()
+        if groups not in (1, in_channels) or (groups != 1 and in_channels != out_channels):
+            raise NotImplementedError("only dense and depthwise convolutions are on the HIP path")
+        self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, dilation,
+                              groups, bias=False)
+        self.bn = norm_layer(out_channels)
+        self.depthwise = groups != 1
+
+    def forward(self, act, out=None):
+        if self.depthwise:
+            return F.dwconv_bn(act, self.conv, self.bn, out=out)
+        return F.conv_bn(act, self.conv, self.bn, out=out)
+
+
+class _BNPReLU(nn.Module):
+    """BN -> PReLU of a materialised tensor (basic.py:108-117): CGNet's stage concats.  x: plain
+    NHWC buffer of round_up8(out_channels) channels, zeros beyond out_channels; returns the same."""
+
+    def __init__(self, out_channels, norm_layer=nn.BatchNorm2d):
+        super().__init__()
+        self.bn = norm_layer(out_channels)
+        self.prelu = nn.PReLU(out_channels)
+
+    def forward(self, x, out=None):
+        return F.bn_prelu(F.bn_of_concat(x, self.bn, self.prelu.weight.numel()), self.prelu,
+                          out=out)
 
 
 class InvertedResidual(nn.Module):
