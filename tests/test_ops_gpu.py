@@ -734,6 +734,40 @@ def test_errors_are_reported_not_fatal():
     torch.cuda.synchronize()  # (nothing was launched, nothing faulted)
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_criss_cross_attention_argument_errors_are_reported_not_fatal(dtype):
+    """csrc/cca.hip refuses, with the library's error and before any launch: more than 512
+    attended entries (the eight trips of the dot kernels), a channel count or a row pitch that is
+    not a multiple of the 16-byte vector.  Every tensor is real and of the stated shape."""
+    vec = 8 if dtype == torch.bfloat16 else 4
+    z = lambda *s: torch.zeros(s, dtype=dtype, device=DEV)
+    # H + W - 1 = 513, in each of the three entry points
+    q, att = z(1, 2, 512, vec), torch.zeros((1, 2, 512, 513), device=DEV)
+    with pytest.raises(RuntimeError, match="cca_attention: H \\+ W - 1 = 513 exceeds 512"):
+        K().cca_attention(q, q)
+    with pytest.raises(RuntimeError, match="cca_attention_bwd: H \\+ W - 1 = 513 exceeds 512"):
+        K().cca_attention_bwd(q, q, att)
+    with pytest.raises(RuntimeError, match="cca_map: H \\+ W - 1 = 513 exceeds 512"):
+        K().cca_map(att, q)
+    # (512 entries are served: tests/test_attention_gpu.py)
+    # C not a multiple of the channel vector
+    odd, att = z(1, 4, 5, vec + vec // 2), torch.zeros((1, 4, 5, 8), device=DEV)
+    for call in (lambda: K().cca_attention(odd, odd), lambda: K().cca_attention_bwd(odd, odd, att),
+                 lambda: K().cca_map(att, odd)):
+        with pytest.raises(RuntimeError, match="must be multiples of %d" % vec):
+            call()
+    # a pitch that is not a vector multiple: input, second input, residual
+    ok = z(1, 4, 5, vec)
+    pitched = z(1, 4, 5, vec + vec // 2)[..., :vec]
+    for call in (lambda: K().cca_attention(pitched, ok), lambda: K().cca_attention(ok, pitched),
+                 lambda: K().cca_attention_bwd(ok, pitched, att), lambda: K().cca_map(att, pitched)):
+        with pytest.raises(RuntimeError, match="must be multiples of %d" % vec):
+            call()
+    with pytest.raises(RuntimeError, match="bad residual pitch"):
+        K().cca_map(att, ok, res=pitched)
+    torch.cuda.synchronize()  # (nothing was launched, nothing faulted)
+
+
 # ------------------------------------------------------------------------------ BN fold
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("O,C", [(136, 200), (728, 728), (40, 72), (19, 50), (256, 2048)])
