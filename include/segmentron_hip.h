@@ -649,6 +649,49 @@ int seg_fold_bwd_finalize_sync(void* p2p, const float* dsdt, int rows, const dou
                                const float* scale, float* dgamma, float* dbeta, float* c0,
                                float* c1, int C, double grad_scale, void* stream);
 
+/* ---- LEDNet: dense 3-tap line convolutions and the split-shuffle tail (csrc/conv_line.hip) ----
+ * Replace the nn.Conv2d (3,1) / (1,3) layers of SSnbt.branch1 / branch2
+ * (segmentron/models/lednet.py:76-102: stride 1, padding = dilation along ONE axis, no bias):
+ *   y[n,h,w,o] = sum_t sum_c act(x[n, h + (t-1)*dil*[axis==0], w + (t-1)*dil*[axis==1], c])
+ *                            * wp[o][t][c]  (+ add[n,h,w,o])
+ * NHWC, C == O in {16, 32, 64}, axis 0 = H (a [O,C,3,1] parameter), 1 = W ([O,C,1,3]); wp is the
+ * [O][3*C] packing seg_conv_gemm_fwd takes, in `dtype`.  x, y and add have their own row pitches
+ * (channel slices of wider buffers); channels outside the slice are never touched.  The prologue
+ * is applied in float32 and, for bf16, rounded once before the MFMA; a tap outside its own image
+ * (axis 0) or row (axis 1) is zero AFTER the prologue.  add (nullable): y = acc + add, rounded
+ * once.  stat_partial (nullable): fp32 [rows][2][C], rows = seg_conv_line_geom(.., 1), sums and
+ * sums of squares of the values AS STORED (after add and rounding), for seg_bn_finalize_p.
+ * The data gradient is the same call on dy with the weights repacked as [C][2-t][O].
+ *   seg_conv_line_ok   : 1 if the kernels serve (dtype, C, axis, dil); pure host query
+ *   seg_conv_line_geom : what = 0 pixels per tile, 1 grid (= partial rows), 2 tiles per block,
+ *                        3 pixels per staging trip of the weight gradient; -1 on bad input
+ *   seg_conv_line_wgrad: partial fp32 [splits][O][C][3] (splits from seg_conv_line_wgrad_splits;
+ *                        the memory layout of the [O,C,3,1] / [O,C,1,3] parameter itself),
+ *                        dW[o][c][t] = sum_p dy[p][o] * act(x)[p + tap t][c]; sum with seg_colsum.
+ * No atomics, fixed summation order: every launch is bit-identical.                            */
+int seg_conv_line_ok(int dtype, int C, int axis, int dil);
+int seg_conv_line_geom(int dtype, int N, int H, int W, int C, int what);
+int seg_conv_line_wgrad_splits(int dtype, int N, int H, int W, int C);
+int seg_conv_line_fwd(int dtype, const void* x, long ldx, int N, int H, int W, int C,
+                      const void* wp, int axis, int dil, int pro_mode, const float* pro_scale,
+                      const float* pro_shift, void* y, long ldy, const void* add, long ldadd,
+                      float* stat_partial, void* stream);
+int seg_conv_line_wgrad(int dtype, const void* x, long ldx, const void* dy, long lddy, int N,
+                        int H, int W, int C, int axis, int dil, int pro_mode,
+                        const float* pro_scale, const float* pro_shift, float* partial, int splits,
+                        void* stream);
+/* SSnbt.forward's tail (lednet.py:117-128: the two branches' last BatchNorm + ReLU, torch.cat,
+ * + x, ReLU, channel_shuffle(groups=2)) in one pass over P = N*H*W pixels, C in {32, 64, 128}:
+ *   out[p][2i + g] = relu(relu(y_g[p][i]*s_g[i] + t_g[i]) + x[p][g*C/2 + i]),  g < 2, i < C/2
+ * and its backward, unshuffled:  gm[p][g*C/2 + i] = gout[p][2i + g] * (out[p][2i + g] > 0).
+ *   seg_ssnbt_tail_geom: what = 0 threads, 1 grid, 2 loop trips; -1 on bad input                */
+int seg_ssnbt_tail_geom(int dtype, long P, int C, int what);
+int seg_ssnbt_tail_fwd(int dtype, const void* y0, long ldy0, const float* s0, const float* t0,
+                       const void* y1, long ldy1, const float* s1, const float* t1, const void* x,
+                       long ldx, void* out, long ldout, long P, int C, void* stream);
+int seg_ssnbt_tail_bwd(int dtype, const void* gout, long ldgout, const void* out, long ldout,
+                       void* gm, long ldgm, long P, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

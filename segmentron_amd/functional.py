@@ -1647,6 +1647,17 @@ def conv_bn(act, conv, bn=None, out=None, fork=None, park=None):
     `park` (or the input's own `Act.park`): the GradFork this conv parks ITS input gradient in,
     for the fork's other consumer to add."""
     x = act.t
+    if conv.groups == 1 and not (conv.kernel_size[0] == conv.kernel_size[1]
+                                 and conv.padding[0] == conv.padding[1]
+                                 and conv.dilation[0] == conv.dilation[1]
+                                 and conv.stride[0] == conv.stride[1]):
+        # the implicit GEMM takes ONE pad / dilation / stride for both axes: reading index 0 would
+        # silently compute another convolution
+        raise NotImplementedError(
+            "conv_bn: kernel_size %s / stride %s / padding %s / dilation %s differ between the "
+            "axes; the implicit GEMM has one geometry for both (3-tap factorised convolutions: "
+            "line_conv_bn)" % (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding),
+                               tuple(conv.dilation)))
     if park is None:
         park = act.park
     gn = bn if is_group_norm(bn) else None
@@ -2049,6 +2060,198 @@ def cg_joint_bn(t, f_loc, f_sur, bn):
     spec = CGJointSpec(d, uses_batch_stats(bn), cg_joint_routed(t.dtype, C, d))
     y = _CGJointFn.apply(t, f_loc.weight, f_sur.weight, spec)
     return Act(y, finish_bn(bn, spec.partial, N * H * W, y=y))
+
+
+# ---- LEDNet: 3-tap line convolutions and the split-shuffle tail (csrc/conv_line.hip) -----------
+class BlockGrad:
+    """Meeting point of the three gradients of an SSnbt block input (lednet.py:117-128: the two
+    channel halves and the residual).  The tail's backward parks the unshuffled masked gradient
+    `gm` here (all of it is the residual gradient); the data-gradient launch of each branch's
+    FIRST convolution stores into its half of one [N,H,W,C] buffer `dx` and adds the matching
+    half of gm in its epilogue; `_SplitFn.backward` returns the buffer.  No slice backward
+    (zero-fill + copy) and no element-wise add."""
+    __slots__ = ("gm", "dx", "added")
+
+    def __init__(self):
+        self.gm, self.dx, self.added = None, None, [False, False]
+
+
+class _SplitFn(torch.autograd.Function):
+    """x.split(C // 2, channel) as two views whose gradients arrive as the halves of one buffer."""
+
+    @staticmethod
+    def forward(ctx, x, bg):
+        ctx.bg = bg
+        ctx.set_materialize_grads(False)
+        h = x.shape[-1] // 2
+        return x[..., :h], x[..., h:]
+
+    @staticmethod
+    def backward(ctx, g0, g1):
+        bg = ctx.bg
+        dx, gm, added = bg.dx, bg.gm, bg.added
+        bg.dx, bg.gm, bg.added = None, None, [False, False]
+        if dx is not None and g0 is not None and g1 is not None and all(added):
+            h = g0.shape[-1]
+            if g0.data_ptr() == dx.data_ptr() \
+                    and g1.data_ptr() == dx.data_ptr() + h * dx.element_size():
+                return dx, None
+        # (a branch that took no part in this backward pass: plain tensor arithmetic)
+        gs = [g for g in (g0, g1) if g is not None]
+        if not gs:
+            return gm, None
+        out = torch.cat([g if g is not None else torch.zeros_like(gs[0]) for g in (g0, g1)], -1)
+        if gm is not None:
+            h = out.shape[-1] // 2
+            for i in range(2):
+                if not added[i]:
+                    out[..., i * h:(i + 1) * h] += gm[..., i * h:(i + 1) * h]
+        return out, None
+
+
+def split_halves(x, bg):
+    return _SplitFn.apply(x, bg)
+
+
+def _line_geometry(conv):
+    """(axis, dilation) of a factorised nn.Conv2d: kernel (3,1) -> K.AXIS_H, (1,3) -> K.AXIS_W;
+    stride 1, padding = dilation along that axis only, no bias, C == O."""
+    ks = tuple(conv.kernel_size)
+    if ks not in ((3, 1), (1, 3)):
+        raise NotImplementedError("line_conv_bn: kernel_size %s is not (3,1) / (1,3)" % (ks,))
+    axis = K.AXIS_H if ks == (3, 1) else K.AXIS_W
+    d = conv.dilation[axis]
+    if (conv.groups != 1 or conv.bias is not None or tuple(conv.stride) != (1, 1)
+            or conv.padding[axis] != d or conv.padding[1 - axis] != 0
+            or conv.dilation[1 - axis] != 1 or conv.in_channels != conv.out_channels
+            or conv.padding_mode != "zeros"):
+        raise NotImplementedError("line_conv_bn: %r is not a dense same-size 3-tap convolution "
+                                  "without bias" % (conv,))
+    return axis, d
+
+
+class LineSpec:
+    def __init__(self, act, axis, dil, out, want_stats, first, half):
+        self.bn_in, self.relu, self.pro = act.bn, act.relu, act.pro
+        self.axis, self.dil, self.out, self.want_stats = axis, dil, out, want_stats
+        self.first, self.half = first, half
+        self.partial = None
+
+
+class _LineConvFn(torch.autograd.Function):
+    """nn.Conv2d (3,1) / (1,3) on a deferred activation: csrc/conv_line.hip.  The data gradient is
+    the same kernel on dy with the weights repacked [C][2-t][O]; the weight gradient re-applies the
+    forward prologue."""
+
+    @staticmethod
+    def forward(ctx, x, in_gamma, in_beta, weight, spec):
+        C, dt = x.shape[-1], x.dtype
+        wp = cached_pack(weight, ("fwd", C, dt), lambda: pack_conv_weight(weight, C, dt))
+        y, spec.partial = K.conv_line(x, wp, spec.axis, spec.dil, spec.pro, out=spec.out,
+                                      want_stats=spec.want_stats)
+        spec.out = None  # (it IS y: see _ConvFn)
+        ctx.spec = spec
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        s = ctx.spec
+        C, dt = x.shape[-1], x.dtype
+        if dy.dtype != dt or not _sum_n_operand_ok(dy, K.vec_of(dt)):
+            dy = dy.to(dt).contiguous()
+        dW = K.conv_line_wgrad(x, dy, s.axis, s.dil, s.pro).view(weight.shape)
+        dx = dgamma = dbeta = None
+        if ctx.needs_input_grad[0]:
+            wt = cached_pack(weight, ("dgrad", C, dt, C),
+                             lambda: pack_conv_weight_dgrad(weight, C, dt))
+            bg = s.first
+            if bg is not None:  # the block's first convolution: see BlockGrad
+                N, H, W, _ = x.shape
+                if bg.dx is None:
+                    bg.dx = torch.empty((N, H, W, 2 * C), dtype=dt, device=x.device)
+                sl = slice(s.half * C, (s.half + 1) * C)
+                add = bg.gm[..., sl] if bg.gm is not None else None
+                dx, _ = K.conv_line(dy, wt, s.axis, s.dil, out=bg.dx[..., sl], add=add)
+                bg.added[s.half] = add is not None
+            else:
+                g, _ = K.conv_line(dy, wt, s.axis, s.dil)
+                dx, dgamma, dbeta = bn_input_backward(g, x, s.bn_in, s.relu, inplace=True)
+        return dx, dgamma, dbeta, dW, None
+
+
+def line_conv_bn(act, conv, bn=None, out=None, first=None, half=0):
+    """Factorised 3-tap conv (nn.Conv2d (3,1) / (1,3), see _line_geometry) [+ BatchNorm
+    statistics] -> an Act whose BN (if any) is pending; the caller sets ``.relu``.  `first`: the
+    BlockGrad of the SSnbt block whose input half `half` (0 / 1) this convolution reads — its
+    input must be plain."""
+    axis, d = _line_geometry(conv)
+    x = act.t
+    if not K.conv_line_ok(x.dtype, x.shape[-1], axis, d) or x.shape[-1] != conv.in_channels:
+        raise NotImplementedError("line_conv_bn: no kernel for %s with %d channels at dilation %d"
+                                  % (x.dtype, x.shape[-1], d))
+    if is_group_norm(bn):
+        raise NotImplementedError("line_conv_bn: GroupNorm is not served here")
+    if first is not None and (act.bn is not None or act.relu):
+        raise ValueError("line_conv_bn: the first convolution of a block reads its plain input")
+    spec = LineSpec(act, axis, d, out, bn is not None and uses_batch_stats(bn), first, half)
+    g, b = act.params
+    y = _LineConvFn.apply(x, g, b, conv.weight, spec)
+    if bn is None:
+        return Act(y)
+    N, H, W, _ = y.shape
+    return Act(y, finish_bn(bn, spec.partial, N * H * W, y=y))
+
+
+class TailSpec:
+    def __init__(self, a0, a1, bg, out):
+        self.bn0, self.bn1, self.bg, self.out = a0.bn, a1.bn, bg, out
+
+
+class _SSnbtTailFn(torch.autograd.Function):
+    """out = channel_shuffle(relu(cat(relu(bn(y0)), relu(bn(y1))) + x), 2) in one pass
+    (seg_ssnbt_tail_fwd).  Backward: one masked, unshuffling pass (seg_ssnbt_tail_bwd) whose
+    halves enter the two BatchNorm backward chains as channel slices and whose whole is the
+    residual gradient (parked in the BlockGrad for the first convolutions' epilogues)."""
+
+    @staticmethod
+    def forward(ctx, y0, g0, b0, y1, g1, b1, x, spec):
+        out = K.ssnbt_tail_fwd(y0, spec.bn0.scale, spec.bn0.shift, y1, spec.bn1.scale,
+                               spec.bn1.shift, x, out=spec.out)
+        spec.out = None
+        ctx.spec = spec
+        ctx.save_for_backward(y0, y1, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        y0, y1, out = ctx.saved_tensors
+        s = ctx.spec
+        if gout.dtype != out.dtype or not _sum_n_operand_ok(gout, K.vec_of(out.dtype)):
+            gout = gout.to(out.dtype).contiguous()
+        gm = K.ssnbt_tail_bwd(gout, out)
+        h = out.shape[-1] // 2
+        d0, dg0, db0 = bn_input_backward(gm[..., :h], y0, s.bn0, True)
+        d1, dg1, db1 = bn_input_backward(gm[..., h:], y1, s.bn1, True)
+        gx = None
+        if ctx.needs_input_grad[6]:
+            if s.bg is not None:
+                s.bg.gm = gm
+            else:
+                gx = gm
+        return d0, dg0, db0, d1, dg1, db1, gx, None
+
+
+def ssnbt_tail(a0, a1, x, bg=None, out=None):
+    """a0, a1: the two branch outputs (Acts with a pending BatchNorm and ReLU), x: the block's
+    plain input -> the block's plain output.  bg: the BlockGrad shared with split_halves and the
+    branches' first convolutions."""
+    if a0.bn is None or a1.bn is None or not (a0.relu and a1.relu):
+        raise ValueError("ssnbt_tail: both branches end in BatchNorm + ReLU")
+    g0, b0 = a0.params
+    g1, b1 = a1.params
+    return _SSnbtTailFn.apply(a0.t, g0, b0, a1.t, g1, b1, x, TailSpec(a0, a1, bg, out))
 
 
 def max_pool(act, k, stride, pad):

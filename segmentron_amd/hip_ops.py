@@ -1484,3 +1484,98 @@ def point_ce_bwd(rows, target, ignore_index, loss_out, grad_out):
     LIB.call("seg_point_ce_bwd", _DT[rows.dtype], _p(rows), ld, R, C, _p(target.contiguous()),
              int(ignore_index), _p(loss_out), _p(grad_out), _p(dx), C, _stream())
     return dx
+
+
+# ---- LEDNet: 3-tap line convolutions and the split-shuffle tail (csrc/conv_line.hip) ------------
+AXIS_H, AXIS_W = 0, 1
+
+
+def conv_line_ok(dtype, C, axis, dil):
+    return dtype in _DT and LIB.query("seg_conv_line_ok", _DT[dtype], C, axis, dil) == 1
+
+
+def conv_line_geom(dtype, N, H, W, C):
+    """Launch geometry of conv_line on [N,H,W,C]: pixels per tile, grid (= statistic rows), tiles
+    per block, pixels per weight-gradient trip, weight-gradient splits."""
+    vals = [LIB.query("seg_conv_line_geom", _DT[dtype], N, H, W, C, k) for k in range(4)]
+    vals.append(LIB.query("seg_conv_line_wgrad_splits", _DT[dtype], N, H, W, C))
+    if min(vals) < 1:
+        raise ValueError("conv_line_geom: bad dtype / shape: %s %s" % (dtype, (N, H, W, C)))
+    return dict(zip(("tile", "grid", "tiles_per_block", "wgrad_trip", "wgrad_splits"), vals))
+
+
+def conv_line(x, wp, axis, dil, pro=None, out=None, add=None, want_stats=False):
+    """x NHWC [N,H,W,C] (a channel slice is fine); wp [C, 3*C] in x.dtype, taps along `axis`
+    (AXIS_H: a (3,1) kernel, AXIS_W: (1,3)).  Returns (y, stat_partial|None); y = conv (+ add)."""
+    N, H, W, C, ldx = nhwc(x)
+    if not conv_line_ok(x.dtype, C, axis, dil):
+        raise RuntimeError("conv_line: no kernel for %s C=%d axis=%d dil=%d" % (x.dtype, C, axis, dil))
+    assert wp.dtype == x.dtype and wp.is_contiguous() and tuple(wp.shape) == (C, 3 * C)
+    mode, ps, pt = _pro(pro)
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == (N, H, W, C) and out.dtype == x.dtype
+    ldy = nhwc(out)[4]
+    ldadd = 0
+    if add is not None:
+        assert tuple(add.shape) == (N, H, W, C) and add.dtype == x.dtype
+        ldadd = nhwc(add)[4]
+    partial = None
+    if want_stats:
+        rows = LIB.query("seg_conv_line_geom", _DT[x.dtype], N, H, W, C, 1)
+        partial = torch.empty((rows, 2, C), dtype=torch.float32, device=x.device)
+    LIB.call("seg_conv_line_fwd", _DT[x.dtype], _p(x), ldx, N, H, W, C, _p(wp), axis, dil, mode,
+             _p(ps), _p(pt), _p(out), ldy, _p(add), ldadd, _p(partial), _stream())
+    return out, partial
+
+
+def conv_line_wgrad(x, dy, axis, dil, pro=None):
+    """-> dW fp32 [C, C, 3] = [o][c][tap]: the memory layout of the [O,C,3,1] / [O,C,1,3]
+    parameter."""
+    N, H, W, C, ldx = nhwc(x)
+    Nd, Hd, Wd, Cd, lddy = nhwc(dy)
+    assert (Nd, Hd, Wd, Cd) == (N, H, W, C) and dy.dtype == x.dtype
+    mode, ps, pt = _pro(pro)
+    splits = LIB.query("seg_conv_line_wgrad_splits", _DT[x.dtype], N, H, W, C)
+    if splits < 1:
+        raise RuntimeError("conv_line_wgrad: no kernel for %s C=%d" % (x.dtype, C))
+    partial = torch.empty((splits, 3 * C * C), dtype=torch.float32, device=x.device)
+    LIB.call("seg_conv_line_wgrad", _DT[x.dtype], _p(x), ldx, _p(dy), lddy, N, H, W, C, axis, dil,
+             mode, _p(ps), _p(pt), _p(partial), splits, _stream())
+    if splits == 1:
+        return partial.view(C, C, 3)
+    return colsum(partial, f64=False).view(C, C, 3)
+
+
+def ssnbt_tail_geom(dtype, P, C):
+    vals = [LIB.query("seg_ssnbt_tail_geom", _DT[dtype], P, C, k) for k in range(3)]
+    if min(vals) < 1:
+        raise ValueError("ssnbt_tail_geom: bad dtype / P / C: %s %d %d" % (dtype, P, C))
+    return dict(zip(("threads", "grid", "trips"), vals))
+
+
+def ssnbt_tail_fwd(y0, s0, t0, y1, s1, t1, x, out=None):
+    """out[..., 2i+g] = relu(relu(y_g[..., i]*s_g[i] + t_g[i]) + x[..., g*C/2 + i])."""
+    N, H, W, C, ldx = nhwc(x)
+    h = C // 2
+    assert tuple(y0.shape) == (N, H, W, h) and tuple(y1.shape) == (N, H, W, h)
+    assert y0.dtype == x.dtype and y1.dtype == x.dtype
+    for v in (s0, t0, s1, t1):
+        assert v.dtype == torch.float32 and v.numel() == h and v.is_contiguous()
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=x.dtype, device=x.device)
+    LIB.call("seg_ssnbt_tail_fwd", _DT[x.dtype], _p(y0), nhwc(y0)[4], _p(s0), _p(t0), _p(y1),
+             nhwc(y1)[4], _p(s1), _p(t1), _p(x), ldx, _p(out), nhwc(out)[4], N * H * W, C,
+             _stream())
+    return out
+
+
+def ssnbt_tail_bwd(gout, out, gm=None):
+    """gm[..., g*C/2 + i] = gout[..., 2i+g] * (out[..., 2i+g] > 0)."""
+    N, H, W, C, ldo = nhwc(out)
+    assert tuple(gout.shape) == (N, H, W, C) and gout.dtype == out.dtype
+    if gm is None:
+        gm = torch.empty((N, H, W, C), dtype=out.dtype, device=out.device)
+    LIB.call("seg_ssnbt_tail_bwd", _DT[out.dtype], _p(gout), nhwc(gout)[4], _p(out), ldo, _p(gm),
+             nhwc(gm)[4], N * H * W, C, _stream())
+    return gm

@@ -11,3 +11,4 @@ from .pointrend import PointRend  # noqa: F401
 from .bisenet import BiSeNet  # noqa: F401
 from .dunet import DUNet  # noqa: F401
 from .cgnet import CGNet  # noqa: F401
+from .lednet import LEDNet  # noqa: F401
