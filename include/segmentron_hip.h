@@ -405,6 +405,48 @@ int seg_prelu_bwd(int dtype, const void* g_y, long ldgy, const float* g_pool, co
                   long ldx, const float* scale, const float* shift, const float* alpha, void* g_z,
                   long ldgz, int N, long HW, int C, float* partial, int chunks, void* stream);
 
+/* ---- ESPNetv2's EESP unit and DownSampler (csrc/espnetv2.hip; segmentron/modules/module.py:165-207,
+ * segmentron/models/backbones/eespnet.py:14-43) ---------------------------------------------------
+ * NHWC, fp32 and bf16; every pitch is a multiple of the element type's 16-byte vector (4 / 8).  No
+ * atomics, fp32 partial rows summed in index order, bit-identical results on every launch, and no
+ * image reaches another image's outputs or rows.
+ *   seg_eesp_pyr_fwd     y[..., j*n:(j+1)*n] = sum_{i <= j} depthwise 3x3 (w_i, pad = dilation = d_i,
+ *                        stride) of x for j = 0..3, one pass over x, fp32 sums rounded once; w_i are
+ *                        the [n,1,3,3] parameters as they are; n a positive multiple of 8, each d_i
+ *                        in 1..4 and d0 <= d1 <= d2 <= d3, stride 1 or 2, y has (H-1)/stride + 1
+ *                        rows; anything else is an error.  partial[chunks * N][2][4n] (nullable) =
+ *                        sum | sum of squares of the fp32 values, chunks = seg_eesp_pyr_chunks(...)
+ *                        (or any 1..256)
+ *   seg_eesp_suffix_sum  s[..., j*n:(j+1)*n] = sum_{i >= j} g[..., i*n:(i+1)*n] over rows of 4n
+ *                        channels (what branch j's backward sees); s may be g
+ *   seg_avgpool3x3s2_*   nn.AvgPool2d(3, 2, 1) with count_include_pad: divisor 9 everywhere; C a
+ *                        multiple of the vector; the backward writes every gx once (a gather)
+ *   seg_bn_add_prelu_fwd y = prelu(a * sa + ta + b * sb + tb, alpha); sa / ta and sb / tb nullable in
+ *                        pairs (a plain operand); C a multiple of the vector, chunks as
+ *                        seg_apply_pool_chunks
+ *   seg_bn_add_prelu_bwd z recomputed, g_z = z > 0 ? g : alpha * g (the gradient of both affine
+ *                        operands' outputs), partial[chunks][N][C] = sum over z <= 0 of g * z:
+ *                        dalpha = seg_colsum over the chunks * N rows */
+int seg_eesp_pyr_chunks(int N, int H, int W, int n, int stride);
+int seg_eesp_pyr_fwd(int dtype, const void* x, long ldx, int N, int H, int W, int n,
+                     const float* w0, const float* w1, const float* w2, const float* w3, int d0,
+                     int d1, int d2, int d3, int stride, void* y, long ldy, float* partial,
+                     int chunks, void* stream);
+int seg_eesp_suffix_sum(int dtype, const void* g, long ldg, void* s, long lds, long rows, int n,
+                        void* stream);
+int seg_avgpool3x3s2_fwd(int dtype, const void* x, long ldx, int N, int H, int W, int C, void* y,
+                         long ldy, void* stream);
+int seg_avgpool3x3s2_bwd(int dtype, const void* gy, long ldgy, int N, int H, int W, int C, void* gx,
+                         long ldgx, void* stream);
+int seg_bn_add_prelu_fwd(int dtype, const void* a, long lda, const float* sa, const float* ta,
+                         const void* b, long ldb, const float* sb, const float* tb,
+                         const float* alpha, void* y, long ldy, int N, long HW, int C, int chunks,
+                         void* stream);
+int seg_bn_add_prelu_bwd(int dtype, const void* g, long ldg, const void* a, long lda,
+                         const float* sa, const float* ta, const void* b, long ldb, const float* sb,
+                         const float* tb, const float* alpha, void* g_z, long ldgz, int N, long HW,
+                         int C, float* partial, int chunks, void* stream);
+
 /* ---- F.interpolate(mode='bilinear') ---------------------------------------------------------
  * Replaces segmentron/models/deeplabv3_plus.py:39,44,71; segmentron/modules/module.py:64,96;
  * segmentron/models/segbase.py:83.  NHWC -> NHWC with optional prologue and per-(n,c) multiplier. */

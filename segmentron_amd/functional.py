@@ -496,6 +496,23 @@ def pack_conv_weight_dgrad(w, opad, dtype):
     return p.reshape(Cw, KH * KW * opad).to(dtype).contiguous()
 
 
+def block_diag_weight(w, groups):
+    """[O, C/groups, 1, 1] parameter of a grouped 1x1 convolution -> the dense [O, C, 1, 1] weight
+    that computes the same thing: group i's block on the diagonal, exact zeros elsewhere."""
+    O, Cg = w.shape[0], w.shape[1]
+    return torch.block_diag(*w.detach().reshape(groups, O // groups, Cg)).reshape(
+        O, Cg * groups, 1, 1)
+
+
+def block_diag_grad(dW, groups):
+    """Dense weight gradient [O, C] of a block-diagonal 1x1 weight -> its diagonal blocks in the
+    grouped parameter's layout [O, C/groups, 1, 1] (the off-diagonal products are not parameters)."""
+    O, C = dW.shape
+    v = dW.reshape(groups, O // groups, groups, C // groups)
+    return torch.diagonal(v, dim1=0, dim2=2).permute(2, 0, 1).reshape(O, C // groups, 1, 1) \
+        .contiguous()
+
+
 def pack_conv_weight_tconv(w, opad, dtype):
     """-> [Cw, KH*KW*opad] (taps NOT flipped): weights of the transposed-stride gather that
     computes the data gradient of a strided KxK convolution."""
@@ -551,6 +568,7 @@ class ConvSpec:
         self.drop_bias = False
         self.fork = None
         self.park = None  # GradFork this conv parks its input gradient in (fork: takes from)
+        self.groups = 1  # > 1: a grouped 1x1, served by a block-diagonal dense weight
 
 
 class _ConvFn(torch.autograd.Function):
@@ -560,7 +578,13 @@ class _ConvFn(torch.autograd.Function):
     def forward(ctx, x, in_gamma, in_beta, weight, bias, spec):
         O, Cw, KH, KW = weight.shape
         cx, dt = x.shape[-1], x.dtype
-        if KH == 1 and KW == 1 and cx == Cw and weight.dtype == torch.float32:
+        G = spec.groups
+        if G > 1:
+            # at these widths (C <= 256) a 1x1 layer is memory-bound even when dense: the extra
+            # products are with exact zeros, and no grouped GEMM is needed
+            wp = cached_pack(weight, ("fwd_bd", G, cx, dt),
+                             lambda: pack_conv_weight(block_diag_weight(weight, G), cx, dt))
+        elif KH == 1 and KW == 1 and cx == Cw and weight.dtype == torch.float32:
             wp = packed_pointwise(weight, False, dt)
         else:
             wp = cached_pack(weight, ("fwd", cx, dt), lambda: pack_conv_weight(weight, cx, dt))
@@ -591,7 +615,10 @@ class _ConvFn(torch.autograd.Function):
         Cx = x.shape[-1]
         Ow = dy_full.shape[-1]  # ragged O: the zero-padded gradient keeps the vector kernels usable
         dWp = K.conv_wgrad(x, dy_full, Ow, KH, KW, s.stride, s.pad, s.dil, s.pro)[:O]
-        if KH == 1 and KW == 1 and Cx == Cw:
+        G = s.groups
+        if G > 1:
+            dW = block_diag_grad(dWp.view(O, Cx), G)
+        elif KH == 1 and KW == 1 and Cx == Cw:
             dW = dWp.view(O, Cw, 1, 1)
         else:
             dW = dWp.view(O, KH, KW, Cx)[..., :Cw].permute(0, 3, 1, 2).contiguous()
@@ -608,7 +635,10 @@ class _ConvFn(torch.autograd.Function):
                 # the input is a channel-padded buffer (CGNet's 35-channel concat in 40: Cx > Cw):
                 # zero rows, so that the data gradient has the input's width, zeros in its pads
                 return w2d if Cx == Cw else torch.nn.functional.pad(w2d, (0, 0, 0, Cx - Cw))
-            if KH == 1 and KW == 1 and Op == O and Cx == Cw and weight.dtype == torch.float32:
+            if G > 1:
+                wt = cached_pack(weight, ("dgrad_bd", G, Op, dt), lambda: pack_conv_weight_dgrad(
+                    block_diag_weight(weight, G), Op, dt))
+            elif KH == 1 and KW == 1 and Op == O and Cx == Cw and weight.dtype == torch.float32:
                 wt = packed_pointwise(weight, True, dt)
             else:
                 wt = cached_pack(weight, ("dgrad", Op, dt, Cx),
@@ -1641,12 +1671,20 @@ def _conv_materializes_input(act, conv):
 
 
 def conv_bn(act, conv, bn=None, out=None, fork=None, park=None):
-    """conv (nn.Conv2d, groups=1) [+ BatchNorm statistics].  Returns an Act whose BN (if any) and
-    ReLU are pending; caller sets ``.relu``.  `fork`: see GradFork (the input is a forked plain
+    """conv (nn.Conv2d, groups=1, or a grouped 1x1 / stride 1 / unpadded one: served by the dense
+    kernels on a block-diagonal packing of its weight) [+ BatchNorm statistics].  Returns an Act
+    whose BN (if any) and ReLU are pending; caller sets ``.relu``.  `fork`: see GradFork (the input is a forked plain
     activation whose other consumer parks its gradient for this conv's data-gradient GEMM).
     `park` (or the input's own `Act.park`): the GradFork this conv parks ITS input gradient in,
     for the fork's other consumer to add."""
     x = act.t
+    if conv.groups != 1 and not (tuple(conv.kernel_size) == (1, 1) and tuple(conv.stride) == (1, 1)
+                                 and tuple(conv.padding) == (0, 0) and conv.bias is None
+                                 and x.shape[-1] == conv.in_channels):
+        raise NotImplementedError(
+            "conv_bn: groups=%d with kernel_size %s / stride %s / padding %s: only 1x1, stride 1, "
+            "unpadded, bias-free grouped convolutions are served (depthwise 3x3: dwconv_bn)"
+            % (conv.groups, tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding)))
     if conv.groups == 1 and not (conv.kernel_size[0] == conv.kernel_size[1]
                                  and conv.padding[0] == conv.padding[1]
                                  and conv.dilation[0] == conv.dilation[1]
@@ -1668,7 +1706,8 @@ def conv_bn(act, conv, bn=None, out=None, fork=None, park=None):
                     None if gn is not None else out, want_stats=batch_stats)
     g, b = act.params
     foldable = (act.bn is not None and not act.relu and conv.kernel_size == (1, 1)
-                and conv.padding[0] == 0 and conv.bias is None and not _NO_FOLD)
+                and conv.padding[0] == 0 and conv.bias is None and not _NO_FOLD
+                and conv.groups == 1)
     if not foldable and _conv_materializes_input(act, conv):
         # a wide GEMM re-applies the prologue once per 128-column tile of its output
         # (tools/gemm_bench.py: 709 -> 408 TF forward, 419 -> 222 TF weight gradient on
@@ -1687,6 +1726,7 @@ def conv_bn(act, conv, bn=None, out=None, fork=None, park=None):
     else:
         spec.drop_bias = batch_stats and conv.bias is not None
         spec.fork = fork
+        spec.groups = conv.groups
         y = _ConvFn.apply(x, g, b, conv.weight, conv.bias, spec)
         offset = conv.bias.detach() if spec.drop_bias else None
     if gn is not None:
@@ -1710,6 +1750,15 @@ def dwconv_bn(act, conv, bn, out=None, fork=None):
         return group_norm(y, gn, out)
     N, Ho, Wo, _ = y.shape
     return Act(y, finish_bn(bn, spec.partial, N * Ho * Wo, y=y))
+
+
+def dwconv_plain(act, conv, out=None):
+    """Depthwise 3x3 (padding = dilation) with nothing behind it (ESPNetv2's pyramid-pooling
+    stages) -> the plain NHWC output."""
+    assert conv.padding[0] == conv.dilation[0] and conv.kernel_size[0] == 3 and conv.bias is None
+    spec = ConvSpec(act, conv.stride[0], conv.padding[0], conv.dilation[0], out, want_stats=False)
+    g, b = act.params
+    return _DwFn.apply(act.t, g, b, conv.weight, spec)
 
 
 def _bn_backward_is_plain(bn):
@@ -2060,6 +2109,216 @@ def cg_joint_bn(t, f_loc, f_sur, bn):
     spec = CGJointSpec(d, uses_batch_stats(bn), cg_joint_routed(t.dtype, C, d))
     y = _CGJointFn.apply(t, f_loc.weight, f_sur.weight, spec)
     return Act(y, finish_bn(bn, spec.partial, N * H * W, y=y))
+
+
+# ---- ESPNetv2: the EESP depthwise pyramid, its tails and the 3x3/2 average pool (csrc/espnetv2.hip)
+def eesp_pyramid_in_contract(n, dils, stride):
+    """The geometry seg_eesp_pyr_fwd takes (everything else runs per branch)."""
+    dils = tuple(dils)
+    return (len(dils) == 4 and n > 0 and n % 8 == 0 and stride in (1, 2)
+            and all(1 <= d <= 4 for d in dils) and list(dils) == sorted(dils))
+
+
+def eesp_pyramid_routed(dtype, n, dils, stride):
+    """Does the FORWARD of eesp_pyramid run on the joint kernel (csrc/espnetv2.hip) rather than on
+    the per-branch route (four depthwise launches into the channel slices, then the cumulative
+    adds)?  The joint kernel reads x once per distinct tap offset and writes the 4n channels once
+    (5 n-channel passes) where the per-branch route makes about 17.  Measured through this function
+    at the five EESP shapes of a 4 x 512 x 1024 crop (profiles/espnetv2.md, tools/espnetv2_bench.py),
+    joint against per branch in bf16: stride 1 [4,64,128,32] 32.0 against 117.2 us and [4,32,64,64]
+    (dilations 1,1,2,3) 18.0 against 52.2 us; stride 2 [4,256,512,8] 34.0 against 146.5 us,
+    [4,128,256,16] 19.2 against 70.1 us, [4,64,128,32] 13.3 against 69.3 us; 0.21 - 0.40 x in fp32;
+    the captured train step takes 7.85 ms against 8.70 ms.  The joint kernel won at every shape, so
+    it runs wherever the launcher's contract holds; the per-branch route serves every other
+    geometry."""
+    return eesp_pyramid_in_contract(n, dils, stride)
+
+
+class EESPPyrSpec:
+    def __init__(self, dils, stride, want_stats, joint):
+        self.dils, self.stride, self.want_stats, self.joint = tuple(dils), stride, want_stats, joint
+        self.partial = None
+
+
+def _dw_branch_bwd(x, dy, weight, stride, dil):
+    """Backward of one plain-input depthwise 3x3 branch -> (dx contribution, dW [n,1,3,3]): the
+    kernels _DwFn.backward runs for a layer without a pending BatchNorm."""
+    C = weight.shape[0]
+    tiled = K.dw_tiled(stride, dil)
+    if _dw_bwd_is_fused(stride, dil, C, weight.dtype):
+        if stride == 2:
+            g, dW, _ = K.dwconv_bwd_fused_s2(x, dy, weight.detach().contiguous(), None)
+            return g, dW
+        g, dW, _ = K.dwconv_bwd_fused(x, dy, _dw_taps(weight, 1, dil), dil, None,
+                                      torch_layout=tiled)
+    else:
+        dW = K.dwconv_wgrad(x, dy, stride, dil, None, torch_layout=tiled)
+        w = _dw_taps(weight, stride, dil, reversed=stride == 1)
+        g = K.dwconv_dgrad(dy, w, stride, dil, (x.shape[1], x.shape[2]))
+    if not tiled:
+        dW = K.dw_torch_layout(dW)
+    return g, dW
+
+
+class _EESPPyrFn(torch.autograd.Function):
+    """cat_j(sum_{i <= j} spp_dw[i](x)) of the EESP unit (module.py:194-199) with the statistics of
+    br_after_cat's BatchNorm.  Forward: the joint kernel where eesp_pyramid_routed, else the four
+    depthwise launches, each into its channel slice, and the cumulative adds.  Backward: one
+    suffix-sum pass turns the output gradient into the four branch gradients S_j = sum_{i >= j}
+    g_i, then each branch runs the existing depthwise backward on its slice and the four data
+    gradients are summed in one launch."""
+
+    @staticmethod
+    def forward(ctx, x, w0, w1, w2, w3, spec):
+        ws = (w0, w1, w2, w3)
+        N, H, W, n = x.shape
+        s = spec.stride
+        if spec.joint:
+            y, spec.partial = K.eesp_pyramid(x, [w.detach().contiguous() for w in ws], spec.dils,
+                                             s, want_stats=spec.want_stats)
+        else:
+            Ho, Wo = K.conv_out_size(H, 3, s, 1, 1), K.conv_out_size(W, 3, s, 1, 1)
+            y = torch.empty((N, Ho, Wo, 4 * n), dtype=x.dtype, device=x.device)
+            for j, (w, d) in enumerate(zip(ws, spec.dils)):
+                yj = y[..., j * n:(j + 1) * n]
+                if j == 0:
+                    K.dwconv(x, _dw_taps(w, s, d), s, d, None, yj, False)
+                else:  # hierarchical feature fusion: out_k = out_k + output[k - 1]
+                    t, _ = K.dwconv(x, _dw_taps(w, s, d), s, d, None, None, False)
+                    K.sum_n([t, y[..., (j - 1) * n:j * n]], out=yj)
+            spec.partial = K.chan_moments(y) if spec.want_stats else None
+        ctx.spec = spec
+        ctx.save_for_backward(x, *ws)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, *ws = ctx.saved_tensors
+        spec = ctx.spec
+        n = x.shape[-1]
+        if g.dtype != x.dtype or not _sum_n_operand_ok(g, K.vec_of(x.dtype)):
+            g = g.to(x.dtype).contiguous()
+        S = K.eesp_suffix_sum(g)
+        gs, dWs = [], []
+        for j, (w, d) in enumerate(zip(ws, spec.dils)):
+            gj, dW = _dw_branch_bwd(x, S[..., j * n:(j + 1) * n], w, spec.stride, d)
+            gs.append(gj)
+            dWs.append(dW)
+        dx = K.sum_n(gs) if ctx.needs_input_grad[0] else None
+        return (dx, *dWs, None)
+
+
+def eesp_pyramid(t, convs, bn):
+    """t: plain NHWC tensor [N,H,W,n]; convs: the EESP unit's spp_dw (depthwise 3x3 nn.Conv2d of
+    one stride, padding = dilation); bn: br_after_cat's BatchNorm over the concat.
+    -> Act([N,Ho,Wo,len(convs)*n], BatchNorm pending)."""
+    N, H, W, n = t.shape
+    dils = [c.dilation[0] for c in convs]
+    stride = convs[0].stride[0]
+    for c in convs:
+        assert c.kernel_size == (3, 3) and c.groups == n and c.padding[0] == c.dilation[0] \
+            and c.stride[0] == stride and c.bias is None
+    if len(convs) != 4:
+        raise NotImplementedError("eesp_pyramid: k = %d branches (the EESP units served have 4)"
+                                  % len(convs))
+    joint = eesp_pyramid_in_contract(n, dils, stride) and eesp_pyramid_routed(t.dtype, n, dils,
+                                                                              stride)
+    spec = EESPPyrSpec(dils, stride, uses_batch_stats(bn), joint)
+    y = _EESPPyrFn.apply(t, *[c.weight for c in convs], spec)
+    return Act(y, finish_bn(bn, spec.partial, y.shape[0] * y.shape[1] * y.shape[2], y=y))
+
+
+class _AvgPool3x3s2Fn(torch.autograd.Function):
+    """nn.AvgPool2d(3, 2, 1) on a plain NHWC tensor (count_include_pad: divisor 9)."""
+
+    @staticmethod
+    def forward(ctx, x, out):
+        ctx.in_hw = (x.shape[1], x.shape[2])
+        return K.avgpool3x3s2(x, out)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not _sum_n_operand_ok(g, K.vec_of(g.dtype)):
+            g = g.contiguous()
+        return K.avgpool3x3s2_bwd(g, ctx.in_hw), None
+
+
+def avg_pool3x3s2(x, out=None):
+    """x: plain NHWC; out: an NHWC view to write into (a channel slice of a concat buffer)."""
+    return _AvgPool3x3s2Fn.apply(x, out)
+
+
+def _affine_of(bn, lead, C, device):
+    """(scale, shift) fp32 [C] of an operand whose trailing channels carry BatchNorm `bn` behind
+    `lead` plain channels (identity there: scale 1, shift 0) — the padded BatchNorm of the
+    DownSampler's cat([avg, bn(eesp)])."""
+    if bn is None:
+        return None
+    if lead == 0:
+        return bn.scale, bn.shift
+    return (torch.cat([_ones(lead, device), bn.scale]),
+            torch.cat([_const(lead, device, 0.0), bn.shift]))
+
+
+class AddPReLUSpec:
+    def __init__(self, a, b, lead, out):
+        self.bn_a, self.bn_b, self.lead, self.out = a.bn, b.bn, lead, out
+
+
+class _BNAddPReLUFn(torch.autograd.Function):
+    """y = prelu(bn_a(a) + bn_b(b), alpha) written once: the EESP tail module_act(bn(expanded) + x)
+    and the DownSampler tail act(cat[avg, bn(eesp)] + bn(inp_reinf)).  bn_a covers a's channels
+    from `lead` on (the channels before are plain).  Backward: the PReLU mask and dalpha by
+    seg_bn_add_prelu_bwd on the recomputed z; g_z is the gradient of both affine outputs, and each
+    operand's BatchNorm backward is the one every consumer uses (bn_input_backward)."""
+
+    @staticmethod
+    def forward(ctx, a, ga, ba, b, gb, bb, alpha, spec):
+        C = a.shape[-1]
+        al = alpha.detach().float().contiguous()
+        aff_a = _affine_of(spec.bn_a, spec.lead, C, a.device)
+        aff_b = _affine_of(spec.bn_b, 0, C, a.device)
+        y = K.bn_add_prelu(a, b, al, aff_a, aff_b, out=spec.out)
+        spec.out = None
+        ctx.spec = spec
+        ctx.save_for_backward(a, b, al)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, al = ctx.saved_tensors
+        s = ctx.spec
+        C = a.shape[-1]
+        if g.dtype != a.dtype or not _sum_n_operand_ok(g, K.vec_of(a.dtype)):
+            g = g.to(a.dtype).contiguous()
+        g_z, dalpha = K.bn_add_prelu_bwd(g, a, b, al, _affine_of(s.bn_a, s.lead, C, a.device),
+                                         _affine_of(s.bn_b, 0, C, a.device))
+        da = db = dga = dba = dgb = dbb = None
+        if ctx.needs_input_grad[3]:
+            db, dgb, dbb = bn_input_backward(g_z, b, s.bn_b, False)
+        if ctx.needs_input_grad[0]:
+            if s.bn_a is None:
+                da = g_z
+            elif s.lead == 0:
+                da, dga, dba = bn_input_backward(g_z, a, s.bn_a, False)
+            else:  # the plain channels keep g_z; the BatchNorm'd slice is rewritten in place
+                da = g_z if db is None or db.data_ptr() != g_z.data_ptr() else g_z.clone()
+                tail = da[..., s.lead:]
+                _, dga, dba = bn_input_backward(tail, a[..., s.lead:], s.bn_a, False, inplace=True)
+        return da, dga, dba, db, dgb, dbb, dalpha, None
+
+
+def bn_add_prelu(a, b, prelu, lead=0, out=None):
+    """-> plain NHWC prelu(a + b): a, b Acts of one shape whose BatchNorm may be pending (a's, with
+    `lead` > 0, on its channels from `lead` on only: a.t is a concat buffer whose first `lead`
+    channels are plain); prelu: nn.PReLU with one slope per channel."""
+    if a.relu or b.relu:
+        raise ValueError("bn_add_prelu: an operand carries a pending ReLU")
+    if prelu.weight.numel() != a.t.shape[-1]:
+        raise NotImplementedError("bn_add_prelu: one PReLU slope per channel")
+    ga, ba = a.params
+    gb, bb = b.params
+    return _BNAddPReLUFn.apply(a.t, ga, ba, b.t, gb, bb, prelu.weight, AddPReLUSpec(a, b, lead, out))
 
 
 # ---- LEDNet: 3-tap line convolutions and the split-shuffle tail (csrc/conv_line.hip) -----------

@@ -450,9 +450,10 @@ def bn_apply(x, pro_x=None, r=None, pro_r=None, chan_mul=None, post_relu=False, 
     return out
 
 
-def sum_n(tensors):
+def sum_n(tensors, out=None):
     """NHWC tensors of one shape / dtype -> their sum (fp32 accumulation in list order, one
-    rounding): ONE launch for up to 8 operands (more: in groups)."""
+    rounding): ONE launch for up to 8 operands (more: in groups).  out: an NHWC view (a channel
+    slice of a wider buffer, none of the operands) the last launch writes."""
     import ctypes
     ts = list(tensors)
     while len(ts) > 1:
@@ -460,11 +461,15 @@ def sum_n(tensors):
         N, H, W, C, _ = nhwc(group[0])
         lds = [nhwc(t)[4] for t in group]
         assert all(t.shape == group[0].shape and t.dtype == group[0].dtype for t in group)
-        out = torch.empty((N, H, W, C), dtype=group[0].dtype, device=group[0].device)
+        if out is not None and not ts:
+            assert out.shape == group[0].shape and out.dtype == group[0].dtype
+            dst = out
+        else:
+            dst = torch.empty((N, H, W, C), dtype=group[0].dtype, device=group[0].device)
         n = len(group)
-        LIB.call("seg_sum_n", _DT[out.dtype], n, (ctypes.c_void_p * n)(*[t.data_ptr() for t in group]),
-                 (ctypes.c_long * n)(*lds), _p(out), C, N * H * W, C, _stream())
-        ts.insert(0, out)
+        LIB.call("seg_sum_n", _DT[dst.dtype], n, (ctypes.c_void_p * n)(*[t.data_ptr() for t in group]),
+                 (ctypes.c_long * n)(*lds), _p(dst), nhwc(dst)[4], N * H * W, C, _stream())
+        ts.insert(0, dst)
     return ts[0]
 
 
@@ -974,6 +979,138 @@ def cg_joint(x, w_loc, w_sur, dil, out=None, want_stats=True):
     LIB.call("seg_cg_joint_fwd", _DT[x.dtype], _p(x), ldx, N, H, W, C, _p(w_loc), _p(w_sur),
              int(dil), _p(out), nhwc(out)[4], _p(partial), chunks, _stream())
     return out, partial
+
+
+# ---- ESPNetv2's EESP unit and DownSampler (csrc/espnetv2.hip) ------------------------------------
+def _eesp_weights(ws, n):
+    if len(ws) != 4:
+        raise RuntimeError("eesp_pyramid: four branch weights, got %d" % len(ws))
+    for w in ws:
+        if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
+                and tuple(w.shape) == (n, 1, 3, 3)):
+            raise RuntimeError("eesp_pyramid: the weights are contiguous float32 [%d,1,3,3] device "
+                               "tensors, got %s %s" % (n, tuple(w.shape), w.dtype))
+
+
+def eesp_pyramid(x, ws, dils, stride, out=None, want_stats=True):
+    """-> (y [N,Ho,Wo,4n], partial fp32 [rows, 2, 4n] | None): y[..., j*n:(j+1)*n] = the sum over
+    i <= j of the depthwise 3x3 of x with ws[i] (pad = dilation = dils[i], `stride`), one pass over
+    x; partial: sum | sum of squares of the fp32 values for finish_bn.  The launcher refuses n that
+    is no multiple of 8, dilations outside 1..4 or decreasing, and strides other than 1 and 2."""
+    N, H, W, n, ldx = nhwc(x)
+    _eesp_weights(ws, n)
+    dils = [int(d) for d in dils]
+    if len(dils) != 4:
+        raise RuntimeError("eesp_pyramid: four dilations, got %s" % (dils,))
+    stride = int(stride)
+    Ho = (H - 1) // stride + 1 if stride > 0 else 0
+    Wo = (W - 1) // stride + 1 if stride > 0 else 0
+    if out is None:
+        out = torch.empty((N, Ho, Wo, 4 * n), dtype=x.dtype, device=x.device)
+    if tuple(out.shape) != (N, Ho, Wo, 4 * n) or out.dtype != x.dtype:
+        raise RuntimeError("eesp_pyramid out: expected %s %s, got %s %s"
+                           % ((N, Ho, Wo, 4 * n), x.dtype, tuple(out.shape), out.dtype))
+    chunks = LIB.query("seg_eesp_pyr_chunks", N, H, W, n, stride)
+    if chunks < 1:
+        chunks = 1  # (out of contract: the launcher below says what is wrong)
+    partial = torch.empty((chunks * N, 2, 4 * n), dtype=torch.float32, device=x.device) \
+        if want_stats else None
+    LIB.call("seg_eesp_pyr_fwd", _DT[x.dtype], _p(x), ldx, N, H, W, n, _p(ws[0]), _p(ws[1]),
+             _p(ws[2]), _p(ws[3]), dils[0], dils[1], dils[2], dils[3], stride, _p(out),
+             nhwc(out)[4], _p(partial), chunks, _stream())
+    return out, partial
+
+
+def eesp_suffix_sum(g, out=None):
+    """g [N,H,W,4n] -> S with S[..., j*n:(j+1)*n] = sum over i >= j of g's slice i (fp32 sums, one
+    rounding): the gradients the four branches of the pyramid see.  out may be g."""
+    N, H, W, C4, ldg = nhwc(g)
+    if C4 % 4 != 0:
+        raise RuntimeError("eesp_suffix_sum: %d channels are not four slices" % C4)
+    if out is None:
+        out = torch.empty((N, H, W, C4), dtype=g.dtype, device=g.device)
+    if tuple(out.shape) != (N, H, W, C4) or out.dtype != g.dtype:
+        raise RuntimeError("eesp_suffix_sum out: expected %s %s" % ((N, H, W, C4), g.dtype))
+    LIB.call("seg_eesp_suffix_sum", _DT[g.dtype], _p(g), ldg, _p(out), nhwc(out)[4], N * H * W,
+             C4 // 4, _stream())
+    return out
+
+
+def avgpool3x3s2(x, out=None):
+    """nn.AvgPool2d(3, 2, 1) (count_include_pad: divisor 9 everywhere) -> [N, (H-1)//2+1,
+    (W-1)//2+1, C]."""
+    N, H, W, C, ldx = nhwc(x)
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if out is None:
+        out = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
+    if tuple(out.shape) != (N, Ho, Wo, C) or out.dtype != x.dtype:
+        raise RuntimeError("avgpool3x3s2 out: expected %s %s" % ((N, Ho, Wo, C), x.dtype))
+    LIB.call("seg_avgpool3x3s2_fwd", _DT[x.dtype], _p(x), ldx, N, H, W, C, _p(out), nhwc(out)[4],
+             _stream())
+    return out
+
+
+def avgpool3x3s2_bwd(gy, in_hw, out=None):
+    """Gradient of avgpool3x3s2 w.r.t. its [N, H, W, C] input (in_hw = (H, W)): a gather that
+    writes every element once."""
+    N, Ho, Wo, C, ldgy = nhwc(gy)
+    H, W = in_hw
+    if (Ho, Wo) != ((H - 1) // 2 + 1, (W - 1) // 2 + 1):
+        raise RuntimeError("avgpool3x3s2_bwd: gy %s is not the pool of %s" % (tuple(gy.shape), in_hw))
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=gy.dtype, device=gy.device)
+    if tuple(out.shape) != (N, H, W, C) or out.dtype != gy.dtype:
+        raise RuntimeError("avgpool3x3s2_bwd out: expected %s %s" % ((N, H, W, C), gy.dtype))
+    LIB.call("seg_avgpool3x3s2_bwd", _DT[gy.dtype], _p(gy), ldgy, N, H, W, C, _p(out),
+             nhwc(out)[4], _stream())
+    return out
+
+
+def _same_nhwc(t, like, what):
+    if tuple(t.shape) != tuple(like.shape) or t.dtype != like.dtype:
+        raise RuntimeError("%s: expected %s %s, got %s %s"
+                           % (what, tuple(like.shape), like.dtype, tuple(t.shape), t.dtype))
+    return nhwc(t)[4]
+
+
+def bn_add_prelu(a, b, alpha, aff_a=None, aff_b=None, out=None):
+    """y = prelu(a * sa + ta + b * sb + tb, alpha); aff_a = (sa, ta) / aff_b = (sb, tb) fp32 [C],
+    None: that operand is plain."""
+    N, H, W, C, lda = nhwc(a)
+    ldb = _same_nhwc(b, a, "bn_add_prelu b")
+    _chan_param(alpha, C, "bn_add_prelu alpha")
+    sa, ta = aff_a if aff_a is not None else (None, None)
+    sb, tb = aff_b if aff_b is not None else (None, None)
+    for t in (sa, ta, sb, tb):
+        _chan_param(t, C, "bn_add_prelu scale / shift")
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=a.dtype, device=a.device)
+    ldy = _same_nhwc(out, a, "bn_add_prelu out")
+    LIB.call("seg_bn_add_prelu_fwd", _DT[a.dtype], _p(a), lda, _p(sa), _p(ta), _p(b), ldb, _p(sb),
+             _p(tb), _p(alpha), _p(out), ldy, N, H * W, C, _gate_chunks(N, H * W, C), _stream())
+    return out
+
+
+def bn_add_prelu_bwd(g, a, b, alpha, aff_a=None, aff_b=None, out=None):
+    """-> (g_z, dalpha fp32 [C]): z recomputed, g_z = z > 0 ? g : alpha * g (the slope at z == 0 is
+    alpha, as torch), dalpha = sum over z <= 0 of g * z."""
+    N, H, W, C, lda = nhwc(a)
+    ldb = _same_nhwc(b, a, "bn_add_prelu_bwd b")
+    ldg = _same_nhwc(g, a, "bn_add_prelu_bwd g")
+    _chan_param(alpha, C, "bn_add_prelu_bwd alpha")
+    sa, ta = aff_a if aff_a is not None else (None, None)
+    sb, tb = aff_b if aff_b is not None else (None, None)
+    for t in (sa, ta, sb, tb):
+        _chan_param(t, C, "bn_add_prelu_bwd scale / shift")
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=a.dtype, device=a.device)
+    ldgz = _same_nhwc(out, a, "bn_add_prelu_bwd out")
+    chunks = _gate_chunks(N, H * W, C)
+    partial = torch.empty((chunks * N, C), dtype=torch.float32, device=a.device)
+    LIB.call("seg_bn_add_prelu_bwd", _DT[a.dtype], _p(g), ldg, _p(a), lda, _p(sa), _p(ta), _p(b),
+             ldb, _p(sb), _p(tb), _p(alpha), _p(out), ldgz, N, H * W, C, _p(partial), chunks,
+             _stream())
+    return out, colsum(partial, f64=False)
 
 
 def chan_moments(x):

@@ -12,3 +12,4 @@ from .bisenet import BiSeNet  # noqa: F401
 from .dunet import DUNet  # noqa: F401
 from .cgnet import CGNet  # noqa: F401
 from .lednet import LEDNet  # noqa: F401
+from .espnetv2 import ESPNetV2  # noqa: F401

@@ -3,3 +3,4 @@ from .xception import *  # noqa: F401,F403
 from .resnet import *  # noqa: F401,F403
 from .mobilenet import *  # noqa: F401,F403
 from .hrnet import *  # noqa: F401,F403
+from .eespnet import *  # noqa: F401,F403

@@ -76,36 +76,46 @@ class _ConvBNReLU(nn.Module):
 
 
 class _ConvBNPReLU(nn.Module):
-    """conv (groups=1) -> BN -> PReLU (basic.py:80-92).  PReLU is not a prologue the consumers
+    """conv -> BN -> PReLU (basic.py:80-92): dense, grouped 1x1 (ESPNetv2's EESP unit: served by
+    functional.conv_bn on a block-diagonal packing) or depthwise 3x3; any other grouped geometry
+    can be built (state_dict parity) and raises in forward.  PReLU is not a prologue the consumers
     can apply: the activation is written out once (functional.bn_prelu); returns the plain NHWC
     tensor, with `pool` also its global average [N,1,1,C] float32 from the same pass."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
                  groups=1, norm_layer=nn.BatchNorm2d):
         super().__init__()
-        if groups != 1:
-            raise NotImplementedError("only dense convolutions are on the HIP path here")
         self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, dilation,
                               groups, bias=False)
         self.bn = norm_layer(out_channels)
         self.prelu = nn.PReLU(out_channels)
+        self.depthwise = groups != 1 and groups == in_channels == out_channels \
+            and self.conv.kernel_size == (3, 3)
 
     def forward(self, act, pool=False, out=None):
-        return F.bn_prelu(F.conv_bn(act, self.conv, self.bn), self.prelu, pool=pool, out=out)
+        if self.depthwise:
+            a = F.dwconv_bn(act, self.conv, self.bn)
+        else:
+            a = F.conv_bn(act, self.conv, self.bn)
+        return F.bn_prelu(a, self.prelu, pool=pool, out=out)
 
 
 class _ConvBN(nn.Module):
-    """conv (groups=1 or depthwise 3x3) -> BN (basic.py:95-105); returns a deferred activation."""
+    """conv (groups=1, depthwise 3x3, or a grouped 1x1: functional.conv_bn) -> BN
+    (basic.py:95-105); returns a deferred activation."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
                  groups=1, norm_layer=nn.BatchNorm2d, **kwargs):
         super().__init__()
-        if groups not in (1, in_channels) or (groups != 1 and in_channels != out_channels):
-            raise NotImplementedError("only dense and depthwise convolutions are on the HIP path")
         self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, dilation,
                               groups, bias=False)
+        pointwise = self.conv.kernel_size == (1, 1)
+        depthwise = groups == in_channels == out_channels
+        if groups != 1 and not pointwise and not depthwise:
+            raise NotImplementedError("only dense, depthwise 3x3 and grouped 1x1 convolutions are "
+                                      "on the HIP path")
         self.bn = norm_layer(out_channels)
-        self.depthwise = groups != 1
+        self.depthwise = groups != 1 and not pointwise
 
     def forward(self, act, out=None):
         if self.depthwise:

@@ -6,9 +6,9 @@ import torch.nn as nn
 
 from .. import functional as F
 from ..config import cfg
-from .basic import SeparableConv2d, _ConvBNReLU
+from .basic import SeparableConv2d, _BNPReLU, _ConvBN, _ConvBNPReLU, _ConvBNReLU
 
-__all__ = ["_ASPP", "_FCNHead", "PyramidPooling", "PAM_Module", "CAM_Module"]
+__all__ = ["_ASPP", "_FCNHead", "PyramidPooling", "PAM_Module", "CAM_Module", "EESP"]
 
 
 class _FCNHead(nn.Module):
@@ -216,3 +216,58 @@ class CAM_Module(nn.Module):
 
     def forward(self, x):
         return F.channel_attention(x, self.gamma)
+
+
+class EESP(nn.Module):
+    """Extremely efficient spatial pyramid unit of ESPNetv2 (module.py:165-207): grouped 1x1
+    reduce + BN + PReLU, k depthwise 3x3 of growing dilation over the same tensor with hierarchical
+    feature fusion (each branch adds the one before), BN + PReLU over their concat, grouped 1x1
+    expand + BN, then the residual and a PReLU.  Here the pyramid, its fusion, the concat and the
+    statistics of the BatchNorm behind it are one launch (functional.eesp_pyramid,
+    csrc/espnetv2.hip) and the tail BN + residual + PReLU is one pass (functional.bn_add_prelu).
+    x: plain NHWC.  Returns the plain NHWC output — or, for the stride-2 unit inside a DownSampler
+    (`down_method` 'avg'), the raw expansion as an Act whose BatchNorm is pending; `out`: the NHWC
+    view (a channel slice of a concat buffer) the last kernel writes."""
+
+    def __init__(self, in_channels, out_channels, stride=1, k=4, r_lim=7, down_method="esp",
+                 norm_layer=nn.BatchNorm2d):
+        super().__init__()
+        self.stride = stride
+        n = int(out_channels / k)
+        n1 = out_channels - (k - 1) * n
+        assert down_method in ["avg", "esp"], "One of these is suppported (avg or esp)"
+        assert n == n1, "n(={}) and n1(={}) should be equal for Depth-wise Convolution ".format(n, n1)
+        self.proj_1x1 = _ConvBNPReLU(in_channels, n, 1, stride=1, groups=k, norm_layer=norm_layer)
+
+        map_receptive_ksize = {3: 1, 5: 2, 7: 3, 9: 4, 11: 5, 13: 6, 15: 7, 17: 8}
+        self.k_sizes = list()
+        for i in range(k):
+            ksize = int(3 + 2 * i)
+            ksize = ksize if ksize <= r_lim else 3
+            self.k_sizes.append(ksize)
+        self.k_sizes.sort()
+        self.spp_dw = nn.ModuleList()
+        for i in range(k):
+            dilation = map_receptive_ksize[self.k_sizes[i]]
+            self.spp_dw.append(nn.Conv2d(n, n, 3, stride, dilation, dilation=dilation, groups=n,
+                                         bias=False))
+        self.conv_1x1_exp = _ConvBN(out_channels, out_channels, 1, 1, groups=k,
+                                    norm_layer=norm_layer)
+        self.br_after_cat = _BNPReLU(out_channels, norm_layer)
+        self.module_act = nn.PReLU(out_channels)
+        self.downAvg = True if down_method == "avg" else False
+        self.residual = stride == 1 and in_channels == out_channels
+
+    def forward(self, x, out=None):
+        res = None
+        if self.residual:
+            x, res = F.fork(x, 2)
+        t = self.proj_1x1(F.Act(x))
+        pyr = F.eesp_pyramid(t, list(self.spp_dw), self.br_after_cat.bn)
+        cat = F.bn_prelu(pyr, self.br_after_cat.prelu)
+        if self.stride == 2 and self.downAvg:
+            return self.conv_1x1_exp(F.Act(cat), out=out)
+        expanded = self.conv_1x1_exp(F.Act(cat))
+        if res is not None:
+            return F.bn_add_prelu(expanded, F.Act(res), self.module_act, out=out)
+        return F.bn_prelu(expanded, self.module_act, out=out)
