@@ -2,45 +2,26 @@
 schema and decoder list (tests/golden/dunet_state_keys.json, tools/gen_golden_dunet.py) with and
 without the aux head, the drop-in overlay, and the test-side restatement (tests/_dunet_oracle.py)
 against the reference's own runs."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
-import _dunet_oracle as O
-from conftest import GOLDEN
+import _zoo as Z
+from _zoo import DUNET as SPEC
 from oracle import synth
-from test_dropin import _run
 
-YAML = os.path.join(GOLDEN, "cityscapes_dunet.yaml")
+O = SPEC.O
 AUX_PREFIXES = ("auxlayer.", "aux_dupsample.")
-
-
-def dunet_cfg(*overrides):
-    from segmentron_amd.config import cfg, reset_cfg
-    reset_cfg()
-    cfg.update_from_file(YAML)
-    cfg.update_from_list(["TRAIN.BACKBONE_PRETRAINED", "False"] + list(overrides))
-    cfg.PHASE = "test"
-    cfg.check_and_freeze()
-    return cfg
-
-
-def fixture_keys():
-    ref = json.load(open(os.path.join(GOLDEN, "dunet_state_keys.json")))
-    return ref, [(k, tuple(s)) for k, s in ref["keys"]]
 
 
 @pytest.mark.parametrize("aux", [True, False])
 def test_state_dict_schema_equals_reference(aux):
     import segmentron_amd
     from segmentron_amd.config import reset_cfg
-    ref, keys = fixture_keys()
-    assert len(keys) == 354 and ref["n_params"] == 34209768
+    ref, keys = Z.fixture_keys(SPEC)
+    assert len(keys) == SPEC.n_keys and ref["n_params"] == SPEC.n_params  # 354 / 34209768
     assert ref["decoder"] == ["dupsample", "head", "auxlayer", "aux_dupsample"]
-    dunet_cfg("SOLVER.AUX", str(aux))
+    Z.cfg_for(SPEC, "SOLVER.AUX", str(aux))
     try:
         model = segmentron_amd.get_segmentation_model()
         assert type(model).__module__ == "segmentron_amd.models.dunet"
@@ -61,23 +42,7 @@ def test_state_dict_schema_equals_reference(aux):
 
 
 def test_resolves_through_the_overlay():
-    out = _run("""
-        import sys
-        sys.path = [p for p in sys.path if 'reference' not in p]
-        sys.argv = ['x']
-        import segmentron, segmentron_amd
-        from segmentron.config import cfg
-        from segmentron.models.model_zoo import get_segmentation_model, MODEL_REGISTRY
-        assert 'DUNet' in MODEL_REGISTRY.get_list()
-        cfg.update_from_file(%r)
-        cfg.update_from_list(['TRAIN.BACKBONE_PRETRAINED', 'False'])
-        cfg.PHASE = 'test'
-        cfg.check_and_freeze()
-        model = get_segmentation_model()
-        assert type(model).__module__ == 'segmentron_amd.models.dunet', type(model).__module__
-        print('DUNET_OK')
-    """ % YAML, env_extra={"SEGMENTRON_REFERENCE_ROOT": ""})
-    assert "DUNET_OK" in out
+    Z.check_resolves_through_the_overlay(SPEC)
 
 
 def test_oracle_dupsample_is_the_reference_rearrangement():
@@ -92,48 +57,20 @@ def test_oracle_dupsample_is_the_reference_rearrangement():
 
 
 def test_oracle_reproduces_reference_eval_fixture():
-    _, keys = fixture_keys()
-    sd = O.state(keys)
-    outs = O.evaluate(sd, synth.synth_images(O.B, O.H, O.W, seed=0))
-    g = np.load(os.path.join(GOLDEN, "dunet_eval.npz"))
-    assert len(outs) == int(g["n_outputs"]) == 2
-    assert torch.allclose(outs[0][..., ::2, ::2], torch.from_numpy(g["logits0"]), rtol=1e-4,
-                          atol=1e-4)
+    sd, g = Z.check_oracle_eval_fixture(SPEC)
     odd = O.evaluate(sd, synth.synth_images(1, O.H_ODD, O.W_ODD, seed=0))
     assert tuple(odd[0].shape) == tuple(g["shape_odd"]) == (1, 19, 72, 104)
 
 
 def test_oracle_reproduces_reference_train_fixture():
-    _, keys = fixture_keys()
-    sd = O.state(keys)
-    x = synth.synth_images(O.B, O.H, O.W, seed=0)
-    y = synth.synth_targets(O.B, O.H, O.W, seed=0)
-    loss, outs, grads, after = O.train(sd, x, y)
-    t = np.load(os.path.join(GOLDEN, "dunet_train.npz"))
-    assert abs(loss - float(t["loss"])) < 1e-5
-    for i in range(2):
-        assert torch.allclose(outs[i][..., ::2, ::2], torch.from_numpy(t["logits%d" % i]),
-                              rtol=1e-4, atol=1e-4)
-    names = [k[len("gnorm::"):] for k in t.files if k.startswith("gnorm::")]
-    assert len(names) > 150 and set(names) == set(grads)
-    for k in names:
-        n = float(t["gnorm::" + k])
-        assert abs(float(grads[k].double().norm()) - n) <= 1e-3 * max(n, 1e-6) + 1e-9, k
-    stats = [k[len("stat::"):] for k in t.files if k.startswith("stat::")]
-    assert stats
-    for k in stats:
-        ref = torch.from_numpy(t["stat::" + k])
-        if k.endswith("num_batches_tracked"):
-            assert int(after[k]) == int(ref), k
-        else:
-            assert (after[k] - ref).abs().max().item() <= 1e-4 * ref.abs().max().item() + 1e-6, k
+    Z.check_oracle_train_fixture(SPEC)  # (both logits at every 2nd pixel)
 
 
 def test_oracle_reproduces_reference_output_stride_16_fixture():
     """FeatureFused's resize of c2 is real at OUTPUT_STRIDE 16; the output is 8 x c4."""
-    _, keys = fixture_keys()
+    _, keys = Z.fixture_keys(SPEC)
     outs = O.evaluate(O.state(keys), synth.synth_images(O.B, O.H, O.W, seed=0), output_stride=16)
-    g = np.load(os.path.join(GOLDEN, "dunet_os16_eval.npz"))
+    g = np.load(SPEC.file("os16_eval.npz"))
     assert tuple(g["logits0"].shape) == (O.B, 19, O.H // 2, O.W // 2)
     for i in range(2):
         assert torch.allclose(outs[i], torch.from_numpy(g["logits%d" % i]), rtol=1e-4, atol=1e-4)

@@ -2,41 +2,22 @@
 reference's state_dict schema and `exclusive` list (tests/golden/espnetv2_state_keys.json,
 tools/gen_golden_espnetv2.py), the drop-in overlay, conv_bn's refusal of grouped 3x3, and the
 test-side restatement (tests/_espnetv2_oracle.py) against the reference's own runs."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
-import _espnetv2_oracle as O
-from conftest import GOLDEN
+import _zoo as Z
+from _zoo import ESPNETV2 as SPEC
 from oracle import synth
-from test_dropin import _run
 
-YAML = os.path.join(GOLDEN, "cityscapes_espnetv2.yaml")
-
-
-def espnetv2_cfg(*overrides):
-    from segmentron_amd.config import cfg, reset_cfg
-    reset_cfg()
-    cfg.update_from_file(YAML)
-    cfg.update_from_list(["TRAIN.BACKBONE_PRETRAINED", "False"] + list(overrides))
-    cfg.PHASE = "test"
-    cfg.check_and_freeze()
-    return cfg
-
-
-def fixture_keys():
-    ref = json.load(open(os.path.join(GOLDEN, "espnetv2_state_keys.json")))
-    return ref, [(k, tuple(s)) for k, s in ref["keys"]]
+O = SPEC.O
 
 
 def test_yaml_loads_through_cfg():
     from segmentron_amd.config import reset_cfg
     try:
-        cfg = espnetv2_cfg()
+        cfg = Z.cfg_for(SPEC)
         assert cfg.MODEL.MODEL_NAME == "ESPNetV2" and cfg.MODEL.BACKBONE == "eespnet"
         assert tuple(cfg.TRAIN.CROP_SIZE) == (512, 1024) and cfg.TRAIN.BATCH_SIZE == 4
         assert cfg.SOLVER.AUX is False
@@ -47,11 +28,11 @@ def test_yaml_loads_through_cfg():
 def test_state_dict_schema_equals_reference():
     import segmentron_amd
     from segmentron_amd.config import reset_cfg
-    ref, keys = fixture_keys()
-    assert len(keys) == 640 and ref["n_params"] == 2163324
+    ref, keys = Z.fixture_keys(SPEC)
+    assert len(keys) == SPEC.n_keys and ref["n_params"] == SPEC.n_params  # 640 / 2163324
     assert ref["exclusive"] == ["proj_L4_C", "pspMod", "project_l3", "act_l3", "project_l2",
                                 "project_l1"]
-    espnetv2_cfg()
+    Z.cfg_for(SPEC)
     try:
         model = segmentron_amd.get_segmentation_model()
         assert type(model).__module__ == "segmentron_amd.models.espnetv2"
@@ -79,23 +60,7 @@ def test_state_dict_schema_equals_reference():
 
 
 def test_resolves_through_the_overlay():
-    out = _run("""
-        import sys
-        sys.path = [p for p in sys.path if 'reference' not in p]
-        sys.argv = ['x']
-        import segmentron, segmentron_amd
-        from segmentron.config import cfg
-        from segmentron.models.model_zoo import get_segmentation_model, MODEL_REGISTRY
-        assert 'ESPNetV2' in MODEL_REGISTRY.get_list()
-        cfg.update_from_file(%r)
-        cfg.update_from_list(['TRAIN.BACKBONE_PRETRAINED', 'False'])
-        cfg.PHASE = 'test'
-        cfg.check_and_freeze()
-        model = get_segmentation_model()
-        assert type(model).__module__ == 'segmentron_amd.models.espnetv2', type(model).__module__
-        print('ESPNETV2_OK')
-    """ % YAML, env_extra={"SEGMENTRON_REFERENCE_ROOT": ""})
-    assert "ESPNETV2_OK" in out
+    Z.check_resolves_through_the_overlay(SPEC)
 
 
 @pytest.mark.parametrize("kw", [dict(kernel_size=3, padding=1, groups=4),
@@ -139,77 +104,33 @@ def test_pyramid_contract_and_routing():
 
 
 def test_oracle_reproduces_reference_eval_fixture():
-    _, keys = fixture_keys()
-    sd = O.state(keys)
-    g = np.load(os.path.join(GOLDEN, "espnetv2_eval.npz"))
-    outs = O.evaluate(sd, synth.synth_images(O.B, O.H, O.W, seed=0))
-    assert len(outs) == int(g["n_outputs"]) == 1
-    assert torch.allclose(outs[0][..., ::2, ::2], torch.from_numpy(g["logits0"]), rtol=1e-4,
-                          atol=1e-4)
+    sd, g = Z.check_oracle_eval_fixture(SPEC)
     second = O.evaluate(sd, synth.synth_images(1, O.H2, O.W2, seed=0))
     assert tuple(second[0].shape) == (1, 19, O.H2, O.W2)
     assert torch.allclose(second[0][..., ::2, ::2], torch.from_numpy(g["logits0_second"]),
                           rtol=1e-4, atol=1e-4)
 
 
-def _check_train(t, logits_ref, loss, outs, grads, after):
-    assert abs(loss - float(t["loss"])) < 1e-5
-    assert torch.allclose(outs[0][..., ::2, ::2], logits_ref, rtol=1e-4, atol=1e-4)
-    names = [k[len("gnorm::"):] for k in t.files if k.startswith("gnorm::")]
-    assert set(names) == set(grads)
-    for k in names:
-        n = float(t["gnorm::" + k])
-        assert abs(float(grads[k].double().norm()) - n) <= 1e-3 * max(n, 1e-6) + 1e-9, k
-    stats = [k[len("stat::"):] for k in t.files if k.startswith("stat::")]
-    assert stats
-    for k in stats:
-        ref = torch.from_numpy(t["stat::" + k])
-        if k.endswith("num_batches_tracked"):
-            assert int(after[k]) == int(ref) == (0 if O.unused(k) else 1), k
-        else:
-            assert (after[k] - ref).abs().max().item() <= 1e-4 * ref.abs().max().item() + 1e-6, k
-    return names
-
-
-def train_fixture_logits():
-    return torch.cat([torch.from_numpy(np.load(os.path.join(GOLDEN, f))["logits0"])
-                      for f in ("espnetv2_train_logits_a.npz", "espnetv2_train_logits_b.npz")])
-
-
 def test_oracle_reproduces_reference_train_fixture():
-    ref, keys = fixture_keys()
-    sd = O.state(keys)
-    x = synth.synth_images(O.TB, O.TH, O.TW, seed=O.TRAIN_SEED)
-    y = synth.synth_targets(O.TB, O.TH, O.TW, seed=O.TRAIN_SEED)
-    t = np.load(os.path.join(GOLDEN, "espnetv2_train.npz"))
+    names, t = Z.check_oracle_train_fixture(SPEC)
     assert int(t["seed"]) == O.TRAIN_SEED
-    names = _check_train(t, train_fixture_logits(), *O.train(sd, x, y))
-    # the parameters with a gradient are the reference's: level5*, fc (and the module_act a
-    # DownSampler's EESP unit returns before) have none
+    # the parameters with a gradient are the reference's, 256 of 397: level5*, fc (and the
+    # module_act a DownSampler's EESP unit returns before) have none
     assert not any(k.startswith(O.UNUSED) for k in names)
     assert not any(O.unused(k) for k in names)
-    assert len(names) == 256
-    # what the reference's own arithmetic costs on this fixture: the yardsticks of the GPU bars
-    assert 0 < float(t["cpu::grad_global"]) <= 1e-4
-    assert 0 < float(t["cpu::bf16_loss_rel"]) < 1e-2 and 0.99 < float(t["cpu::bf16_grad_cos"]) < 1
 
 
 def test_oracle_reproduces_reference_small_train_fixture():
-    _, keys = fixture_keys()
-    sd = O.state(keys)
-    x = synth.synth_images(O.B, O.H, O.W, seed=0)
-    y = synth.synth_targets(O.B, O.H, O.W, seed=0)
-    t = np.load(os.path.join(GOLDEN, "espnetv2_small_train.npz"))
-    _check_train(t, torch.from_numpy(t["logits0"]), *O.train(sd, x, y))
+    Z.check_oracle_small_train_fixture(SPEC)
 
 
 def test_parameters_with_a_gradient_are_the_references():
     """The model's own parameter names split the way the reference's gradients do."""
     import segmentron_amd
     from segmentron_amd.config import reset_cfg
-    t = np.load(os.path.join(GOLDEN, "espnetv2_train.npz"))
+    t = np.load(SPEC.file("train.npz"))
     with_grad = {k[len("gnorm::"):] for k in t.files if k.startswith("gnorm::")}
-    espnetv2_cfg()
+    Z.cfg_for(SPEC)
     try:
         model = segmentron_amd.get_segmentation_model()
         names = {k for k, _ in model.named_parameters()}

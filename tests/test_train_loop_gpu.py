@@ -22,25 +22,11 @@ import pytest
 import torch
 import torch.nn as nn
 
+from _zoo import MixSoftmaxCrossEntropyLoss
 from conftest import C3_OVERRIDES
 from oracle import synth
 
 pytestmark = pytest.mark.gpu
-
-
-class MixSoftmaxCrossEntropyLoss(nn.CrossEntropyLoss):
-    """Shape of segmentron/solver/loss.py:16-46 (aux outputs weighted by aux_weight)."""
-
-    def __init__(self, aux=False, aux_weight=0.4, ignore_index=-1):
-        super().__init__(ignore_index=ignore_index)
-        self.aux, self.aux_weight = aux, aux_weight
-
-    def forward(self, *inputs, **kwargs):
-        preds, target = tuple(inputs)
-        loss = super().forward(preds[0], target)
-        for p in preds[1:]:
-            loss = loss + self.aux_weight * super().forward(p, target)
-        return dict(loss=loss)
 
 
 def _run_loop(graph, iters, hw, dtype=torch.bfloat16, micro=1):

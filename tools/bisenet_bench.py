@@ -18,31 +18,12 @@ Weights are synthesised (oracle.synth); timings do not depend on them.  Per-kern
 --impl hip --steps 3 --warmup 1` (profiles/bisenet.md).
 """
 import argparse
-import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _bench_zoo as Z
 
 SHAPES = {"train": (8, 768, 768), "eval1": (1, 1024, 2048), "eval8": (8, 1024, 2048)}
 GATE_SHAPES = ((8, 96, 96, 256), (8, 48, 48, 128))
-LEG_TIMEOUT = 420  # seconds per child
-
-
-def timed(fn, steps, warmup):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / steps
 
 
 def build_hip(dtype):
@@ -109,7 +90,7 @@ def model_leg(leg, impl, dtype, steps, warmup):
                 else:
                     with torch.no_grad():
                         O.forward(net, x)
-    return timed(step, steps, warmup)
+    return Z.timed(step, steps, warmup)
 
 
 def gate_leg(impl, dtype, steps, warmup):
@@ -138,7 +119,7 @@ def gate_leg(impl, dtype, steps, warmup):
                 a = TF.conv2d(TF.adaptive_avg_pool2d(xc.float(), 1), w)
                 a = TF.relu(TF.batch_norm(a, None, None, bn.weight, bn.bias, True))
                 (xc * torch.sigmoid(a).to(xc.dtype)).backward(gc)
-        out["%dx%dx%dx%d" % (N, H, W, C)] = round(timed(step, steps, warmup), 4)
+        out["%dx%dx%dx%d" % (N, H, W, C)] = round(Z.timed(step, steps, warmup), 4)
     return out
 
 
@@ -149,8 +130,7 @@ def child(args):
         val = gate_leg(args.impl, dtype, args.steps, args.warmup)
     else:
         val = round(model_leg(args.leg, args.impl, dtype, args.steps, args.warmup), 3)
-    print("RESULT " + json.dumps({"leg": args.leg, "impl": args.impl, "dtype": args.dtype,
-                                  "ms": val, "device": torch.cuda.get_device_name(0)}))
+    Z.emit_result(val)
 
 
 def main():
@@ -166,33 +146,11 @@ def main():
     args = ap.parse_args()
     if args.leg:
         return child(args)
-    res = {"steps": args.steps, "warmup": args.warmup, "shapes": SHAPES, "ms": {}}
-    for leg in args.legs.split(","):
-        for dn in args.dtypes.split(","):
-            for impl in ("hip", "torch"):
-                cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--impl", impl,
-                       "--dtype", dn, "--steps", str(args.steps), "--warmup", str(args.warmup)]
-                try:
-                    p = subprocess.run(cmd, capture_output=True, text=True, timeout=LEG_TIMEOUT)
-                except subprocess.TimeoutExpired:
-                    sys.stderr.write("leg %s/%s/%s ran past %d s: stopping\n"
-                                     % (leg, impl, dn, LEG_TIMEOUT))
-                    return 124
-                line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
-                if p.returncode != 0 or not line:  # nothing more is started on the GPU
-                    sys.stderr.write("leg %s/%s/%s failed (%d): stopping\n%s\n"
-                                     % (leg, impl, dn, p.returncode, p.stderr[-2000:]))
-                    return p.returncode or 1
-                r = json.loads(line[0][len("RESULT "):])
-                res["device"] = r["device"]
-                res["ms"]["%s/%s/%s" % (leg, impl, dn)] = r["ms"]
-                sys.stderr.write("%s/%s/%s: %s\n" % (leg, impl, dn, r["ms"]))
-    text = json.dumps(res)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    return 0
+    header = {"steps": args.steps, "warmup": args.warmup, "shapes": SHAPES}
+    legs = [("%s/%s/%s" % (leg, impl, dn), ["--leg", leg, "--impl", impl, "--dtype", dn])
+            for leg in args.legs.split(",") for dn in args.dtypes.split(",")
+            for impl in ("hip", "torch")]
+    return Z.run_legs(__file__, legs, args, header, results="ms")
 
 
 if __name__ == "__main__":

@@ -25,61 +25,14 @@ ends the run.
 
 Weights and inputs are synthesised; timings do not depend on them."""
 import argparse
-import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _bench_zoo as Z
 
 JOINT_SHAPES = [(4, 192, 192, 32, 2), (4, 96, 96, 64, 4)]  # N, H, W, C, dilation
 PRELU_SHAPE = (4, 96, 96, 128)
 TRAIN_SHAPE = (4, 768, 768)
-LEG_TIMEOUT = 420  # seconds per child
-
-
-def graph_time(fn, iters):
-    """`iters` calls captured into one HIP graph; microseconds per call of one timed replay."""
-    import torch
-    from segmentron_amd.graph import capture
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        with capture(graph, stream=side):
-            for _ in range(iters):
-                fn()
-    torch.cuda.synchronize()
-    graph.replay()
-    torch.cuda.synchronize()
-
-    def once():
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        graph.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / iters
-    return once
-
-
-def _measure(variants, iters, repeats):
-    timers = {name: graph_time(fn, iters) for name, fn in variants.items()}
-    samples = {name: [] for name in variants}
-    for _ in range(repeats):  # interleaved: drift hits every variant alike
-        for name, once in timers.items():
-            samples[name].append(once())
-    res = {}
-    for name, v in samples.items():
-        v = sorted(v)
-        res[name] = {"median_us": round(v[len(v) // 2], 2), "spread_us": round(v[-1] - v[0], 2)}
-    return res
+TRAIN = {"yaml": "cityscapes_cgnet.yaml", "shape": TRAIN_SHAPE, "aux_weight": 0.4}
 
 
 def joint_leg(dtype, iters, repeats):
@@ -131,7 +84,7 @@ def joint_leg(dtype, iters, repeats):
         assert (c2[0].float() - c1[0].float()).abs().max().item() \
             <= 2 * tol * c1[0].float().abs().max().item()
         assert torch.equal(c1[1], c2[1]) and torch.equal(c1[2], c2[2])
-        res = _measure({"joint_fwd": joint_fwd, "composed_fwd": comp_fwd,
+        res = Z.measure({"joint_fwd": joint_fwd, "composed_fwd": comp_fwd,
                         "bwd_pair_sum": bwd_pair_sum, "bwd_pair_res": bwd_pair_res}, iters, repeats)
         eb = x.element_size()
         res["joint_fwd"]["bytes"] = 3 * x.numel() * eb          # read x, write 2C
@@ -191,54 +144,8 @@ def prelu_leg(dtype, iters, repeats):
     assert (yh.float() - ya.permute(0, 2, 3, 1).float()).abs().max().item() \
         <= tol * ya.float().abs().max().item()
     assert (ph.view(N, C) - pa).abs().max().item() <= tol * pa.abs().max().item()
-    return _measure({"hip_fwd": hip_fwd, "hip_fwd_bwd": hip_fwd_bwd, "aten_fwd": aten_fwd,
+    return Z.measure({"hip_fwd": hip_fwd, "hip_fwd_bwd": hip_fwd_bwd, "aten_fwd": aten_fwd,
                      "aten_fwd_bwd": aten_fwd_bwd}, iters, repeats)
-
-
-def train_leg(dtype, steps, warmup, graph):
-    import torch
-    import torch.nn as nn
-    import segmentron_amd
-    from oracle import synth
-    from segmentron_amd.config import cfg, reset_cfg
-    from segmentron_amd.solver.optimizer import get_optimizer
-    os.environ["SEGMENTRON_HIP_GRAPH"] = "1" if graph else "0"
-    reset_cfg()
-    cfg.update_from_file(os.path.join(ROOT, "tests", "golden", "cityscapes_cgnet.yaml"))
-    cfg.update_from_list(["TRAIN.BACKBONE_PRETRAINED", "False"])
-    cfg.PHASE = "train"
-    cfg.check_and_freeze()
-    segmentron_amd.set_compute_dtype(dtype)
-    model = segmentron_amd.get_segmentation_model()
-    model.load_state_dict(synth.synth_like(model.state_dict(), seed=0, conditioned=True))
-    model = model.cuda().train()
-    crit = nn.CrossEntropyLoss(ignore_index=-1)
-    optimizer = get_optimizer(model)
-    B, H, W = TRAIN_SHAPE
-    x = synth.synth_images(B, H, W, seed=0).cuda()
-    y = synth.synth_targets(B, H, W, seed=0).cuda()
-
-    def step():
-        outputs = model(x)
-        loss = crit(outputs[0], y)
-        optimizer.zero_grad()
-        loss.backward()
-        optimizer.step()
-        return loss
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        loss = step()
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) * 1e3 / steps
-    if graph:
-        tg = model._transparent_graph
-        assert tg.disabled is None and len(tg.segments) == 1, tg.disabled
-    assert torch.isfinite(loss)
-    reset_cfg()
-    return {"ms_per_step": round(ms, 3), "img_per_s": round(B * 1e3 / ms, 2)}
 
 
 def child(args):
@@ -249,9 +156,8 @@ def child(args):
     elif args.leg == "prelu":
         val = prelu_leg(dtype, args.iters, args.repeats)
     else:
-        val = train_leg(dtype, args.steps, args.warmup, graph=args.leg == "train_graph")
-    print("RESULT " + json.dumps({"leg": args.leg, "dtype": args.dtype, "value": val,
-                                  "device": torch.cuda.get_device_name(0)}))
+        val = Z.train_leg(TRAIN, dtype, args.steps, args.warmup, graph=args.leg == "train_graph")
+    Z.emit_result(val)
 
 
 def main():
@@ -268,36 +174,13 @@ def main():
     args = ap.parse_args()
     if args.leg:
         return child(args)
-    res = {"joint_shapes": JOINT_SHAPES, "prelu_shape": PRELU_SHAPE, "train_shape": TRAIN_SHAPE,
-           "steps": args.steps, "warmup": args.warmup, "iters": args.iters,
-           "repeats": args.repeats, "results": {}}
-    for leg in args.legs.split(","):
-        for dn in args.dtypes.split(","):
-            if leg.startswith("train") and dn != "bf16":
-                continue
-            cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--dtype", dn,
-                   "--steps", str(args.steps), "--warmup", str(args.warmup), "--iters",
-                   str(args.iters), "--repeats", str(args.repeats)]
-            try:
-                p = subprocess.run(cmd, capture_output=True, text=True, timeout=LEG_TIMEOUT)
-            except subprocess.TimeoutExpired:
-                sys.stderr.write("leg %s/%s ran past %d s: stopping\n" % (leg, dn, LEG_TIMEOUT))
-                return 124
-            line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
-            if p.returncode != 0 or not line:  # nothing more is started on the GPU
-                sys.stderr.write("leg %s/%s failed (%d): stopping\n%s\n"
-                                 % (leg, dn, p.returncode, p.stderr[-3000:]))
-                return p.returncode or 1
-            r = json.loads(line[0][len("RESULT "):])
-            res["device"] = r["device"]
-            res["results"]["%s/%s" % (leg, dn)] = r["value"]
-            sys.stderr.write("%s/%s: %s\n" % (leg, dn, json.dumps(r["value"])))
-    text = json.dumps(res)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    return 0
+    header = {"joint_shapes": JOINT_SHAPES, "prelu_shape": PRELU_SHAPE, "train_shape": TRAIN_SHAPE,
+              "steps": args.steps, "warmup": args.warmup, "iters": args.iters,
+              "repeats": args.repeats}
+    legs = [("%s/%s" % (leg, dn), ["--leg", leg, "--dtype", dn])
+            for leg in args.legs.split(",") for dn in args.dtypes.split(",")
+            if dn == "bf16" or not leg.startswith("train")]
+    return Z.run_legs(__file__, legs, args, header, passed=("steps", "warmup", "iters", "repeats"))
 
 
 if __name__ == "__main__":

@@ -29,17 +29,10 @@ process of its own under a time limit; the first leg that fails ends the run.
 
 Weights and inputs are synthesised; timings do not depend on them."""
 import argparse
-import itertools
 import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import _bench_zoo as Z
 
 # N, H, W, n, stride, dilations: the EESP units of a 4 x 512 x 1024 crop
 PYR_SHAPES = [(4, 64, 128, 32, 1, (1, 2, 3, 4)), (4, 32, 64, 64, 1, (1, 1, 2, 3)),
@@ -50,20 +43,24 @@ POOL_SHAPE = (4, 128, 256, 64)
 GROUPED_SHAPES = [(4, 64, 128, 128, 128), (4, 32, 64, 256, 64)]  # N, H, W, C, O (groups 4)
 TRAIN_SHAPE = (4, 512, 1024)
 ROTATE = 8
-LEG_TIMEOUT = 420  # seconds per child
+
+
+def _state(keys):
+    import _espnetv2_oracle as O
+    return O.state(keys)
+
+
+TRAIN = {"yaml": "cityscapes_espnetv2.yaml", "shape": TRAIN_SHAPE, "aux_weight": 0.4,
+         "state": _state}
 
 
 def _rotating(make, call):
-    """A variant that cycles through ROTATE operand sets built by `make(i)`."""
-    sets = [make(i) for i in range(ROTATE)]
-    it = itertools.cycle(sets)
-    return lambda: call(next(it))
+    return Z.rotating(make, call, ROTATE)
 
 
 def pyramid_leg(iters, repeats):
     import torch
     import torch.nn as nn
-    from cgnet_bench import _measure
     from segmentron_amd import functional as F
     real_routed = F.eesp_pyramid_routed
     out = {}
@@ -98,7 +95,7 @@ def pyramid_leg(iters, repeats):
             variants = {"joint_fwd": _rotating(make, fwd(True)),
                         "per_branch_fwd": _rotating(make, fwd(False)),
                         "bwd": _rotating(make, bwd)}
-            r = _measure(variants, iters, repeats)
+            r = Z.measure(variants, iters, repeats)
             esz = 2 if dtype == torch.bfloat16 else 4
             nbytes = (N * H * W * n + N * Ho * Wo * 4 * n) * esz  # read n once, write 4n once
             for k in ("joint_fwd", "per_branch_fwd"):
@@ -114,7 +111,6 @@ def ops_leg(iters, repeats):
     import torch
     import torch.nn as nn
     import torch.nn.functional as TF
-    from cgnet_bench import _measure
     from segmentron_amd import functional as F
     from segmentron_amd import hip_ops as K
     torch.backends.cudnn.enabled = False
@@ -141,7 +137,7 @@ def ops_leg(iters, repeats):
         y = TF.prelu(a * v[0] + v[1] + b * v[2] + v[3], alpha)
         return torch.autograd.grad(y, [a, b, alpha], ops[2].permute(0, 3, 1, 2))
     mk = lambda i: (rn(N, H, W, C), rn(N, H, W, C), rn(N, H, W, C))
-    r = _measure({
+    r = Z.measure({
         "hip_fwd": _rotating(mk, lambda o: K.bn_add_prelu(o[0], o[1], al, (sa, ta), (sb, tb))),
         "hip_bwd": _rotating(mk, lambda o: K.bn_add_prelu_bwd(o[2], o[0], o[1], al, (sa, ta),
                                                               (sb, tb))),
@@ -159,7 +155,7 @@ def ops_leg(iters, repeats):
     def aten_pool_bwd(ops):
         x = ops[0].permute(0, 3, 1, 2).requires_grad_()
         return torch.autograd.grad(TF.avg_pool2d(x, 3, 2, 1), x, ops[1].permute(0, 3, 1, 2))
-    r = _measure({
+    r = Z.measure({
         "hip_fwd": _rotating(mk, lambda o: K.avgpool3x3s2(o[0])),
         "hip_bwd": _rotating(mk, lambda o: K.avgpool3x3s2_bwd(o[1], (H, W))),
         "aten_fwd": _rotating(mk, lambda o: TF.avg_pool2d(o[0].permute(0, 3, 1, 2), 3, 2, 1)),
@@ -181,7 +177,7 @@ def ops_leg(iters, repeats):
             return lambda o: torch.ops.aten.convolution_backward(
                 o[1].permute(0, 3, 1, 2), o[0].permute(0, 3, 1, 2), wa, None, (1, 1), (0, 0),
                 (1, 1), False, (0, 0), 4, mask)
-        r = _measure({
+        r = Z.measure({
             "hip_fwd": _rotating(mk, lambda o: K.conv_gemm(o[0], wp, O, 1, 1, 1, 0, 1)),
             "hip_dgrad": _rotating(mk, lambda o: K.conv_gemm(o[1], wt, C, 1, 1, 1, 0, 1)),
             "hip_wgrad": _rotating(mk, lambda o: F.block_diag_grad(
@@ -194,84 +190,10 @@ def ops_leg(iters, repeats):
     return out
 
 
-def _model(dtype, phase="train"):
-    import segmentron_amd
-    import _espnetv2_oracle as O
-    from segmentron_amd.config import cfg, reset_cfg
-    from test_espnetv2 import fixture_keys
-    reset_cfg()
-    cfg.update_from_file(os.path.join(ROOT, "tests", "golden", "cityscapes_espnetv2.yaml"))
-    cfg.update_from_list(["TRAIN.BACKBONE_PRETRAINED", "False"])
-    cfg.PHASE = phase
-    cfg.check_and_freeze()
-    segmentron_amd.set_compute_dtype(dtype)
-    model = segmentron_amd.get_segmentation_model()
-    sd = O.state(fixture_keys()[1])
-    model.load_state_dict(sd)
-    return model.cuda().train(), sd
-
-
-def train_leg(dtype, steps, warmup, graph, per_branch=False):
-    import torch
-    import torch.nn as nn
-    from oracle import synth
+def _per_branch():
+    """Every pyramid onto the per-branch route."""
     from segmentron_amd import functional as F
-    from segmentron_amd.config import reset_cfg
-    from segmentron_amd.solver.optimizer import get_optimizer
-    os.environ["SEGMENTRON_HIP_GRAPH"] = "1" if graph else "0"
-    if per_branch:
-        F.eesp_pyramid_routed = lambda *a: False
-    model, _ = _model(dtype)
-    crit = nn.CrossEntropyLoss(ignore_index=-1)
-    optimizer = get_optimizer(model)
-    B, H, W = TRAIN_SHAPE
-    x = synth.synth_images(B, H, W, seed=0).cuda()
-    y = synth.synth_targets(B, H, W, seed=0).cuda()
-
-    def step():
-        outputs = model(x)
-        loss = crit(outputs[0], y)
-        optimizer.zero_grad()
-        loss.backward()
-        optimizer.step()
-        return loss
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        loss = step()
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) * 1e3 / steps
-    if graph:
-        tg = model._transparent_graph
-        assert tg.disabled is None and len(tg.segments) == 1, tg.disabled
-    assert torch.isfinite(loss)
-    reset_cfg()
-    return {"ms_per_step": round(ms, 3), "img_per_s": round(B * 1e3 / ms, 2)}
-
-
-def train_aten_leg(steps, warmup):
-    """The torch restatement on torch's own device kernels, float32 parameters under bf16
-    autocast: forward + cross-entropy + backward (no optimizer step)."""
-    import torch
-    import _espnetv2_oracle as O
-    from oracle import synth
-    from test_espnetv2 import fixture_keys
-    torch.backends.cudnn.enabled = False
-    sd = {k: v.cuda() for k, v in O.state(fixture_keys()[1]).items()}
-    B, H, W = TRAIN_SHAPE
-    x = synth.synth_images(B, H, W, seed=0).cuda()
-    y = synth.synth_targets(B, H, W, seed=0).cuda()
-    for _ in range(warmup):
-        O.train(sd, x, y, autocast=True)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        O.train(sd, x, y, autocast=True)
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) * 1e3 / steps
-    return {"ms_per_step": round(ms, 3), "img_per_s": round(B * 1e3 / ms, 2)}
+    F.eesp_pyramid_routed = lambda *a: False
 
 
 def child(args):
@@ -281,12 +203,13 @@ def child(args):
     elif args.leg == "ops":
         val = ops_leg(args.iters, args.repeats)
     elif args.leg == "train_aten":
-        val = train_aten_leg(args.steps, args.warmup)
+        from _zoo import ESPNETV2
+        val = Z.train_aten_leg(ESPNETV2, TRAIN_SHAPE, args.steps, args.warmup)
     else:
-        val = train_leg(torch.bfloat16, args.steps, args.warmup, graph=args.leg != "train_eager",
-                        per_branch=args.leg == "train_graph_per_branch")
-    print("RESULT " + json.dumps({"leg": args.leg, "value": val,
-                                  "device": torch.cuda.get_device_name(0)}))
+        hook = _per_branch if args.leg == "train_graph_per_branch" else None
+        val = Z.train_leg(TRAIN, torch.bfloat16, args.steps, args.warmup,
+                          graph=args.leg != "train_eager", before_build=hook)
+    Z.emit_result(val)
 
 
 def main():
@@ -302,34 +225,12 @@ def main():
     args = ap.parse_args()
     if args.leg:
         return child(args)
-    res = {"pyramid_shapes": PYR_SHAPES, "add_shape": ADD_SHAPE, "pool_shape": POOL_SHAPE,
-           "grouped_shapes": GROUPED_SHAPES, "train_shape": TRAIN_SHAPE, "rotate": ROTATE,
-           "steps": args.steps, "warmup": args.warmup, "iters": args.iters,
-           "repeats": args.repeats, "results": {}}
-    for leg in args.legs.split(","):
-        cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--steps", str(args.steps),
-               "--warmup", str(args.warmup), "--iters", str(args.iters), "--repeats",
-               str(args.repeats)]
-        try:
-            p = subprocess.run(cmd, capture_output=True, text=True, timeout=LEG_TIMEOUT)
-        except subprocess.TimeoutExpired:
-            sys.stderr.write("leg %s ran past %d s: stopping\n" % (leg, LEG_TIMEOUT))
-            return 124
-        line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
-        if p.returncode != 0 or not line:  # nothing more is started on the GPU
-            sys.stderr.write("leg %s failed (%d): stopping\n%s\n" % (leg, p.returncode,
-                                                                     p.stderr[-3000:]))
-            return p.returncode or 1
-        r = json.loads(line[0][len("RESULT "):])
-        res["device"] = r["device"]
-        res["results"][leg] = r["value"]
-        sys.stderr.write("%s: %s\n" % (leg, json.dumps(r["value"])))
-    text = json.dumps(res)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    return 0
+    header = {"pyramid_shapes": PYR_SHAPES, "add_shape": ADD_SHAPE, "pool_shape": POOL_SHAPE,
+              "grouped_shapes": GROUPED_SHAPES, "train_shape": TRAIN_SHAPE, "rotate": ROTATE,
+              "steps": args.steps, "warmup": args.warmup, "iters": args.iters,
+              "repeats": args.repeats}
+    legs = [(leg, ["--leg", leg]) for leg in args.legs.split(",")]
+    return Z.run_legs(__file__, legs, args, header, passed=("steps", "warmup", "iters", "repeats"))
 
 
 if __name__ == "__main__":

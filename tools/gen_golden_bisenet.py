@@ -19,80 +19,54 @@ The training batch is 4: the attention BatchNorms normalise N values per channel
 the output is the sign of a difference.  Before anything is written the float32 run is compared
 with the reference in float64: global gradient error <= 1e-4, worst tensor <= 5e-4.
 
-    python tools/gen_golden_bisenet.py          (the OS 32 leg runs in a second process: the
-                                                 reference's cfg is a frozen per-process singleton)
+    python tools/gen_golden_bisenet.py [--out DIR]   (the OS 32 leg runs in a second process: the
+                                                      reference's cfg is a frozen per-process
+                                                      singleton)
 """
-import json
 import os
-import shutil
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
+import _golden_zoo as G
+
 YAML = "configs/cityscapes_bisenet.yaml"
 
 
-def _no_dropout(model):
-    import torch.nn as nn
-    for m in model.modules():
-        if isinstance(m, nn.Dropout):
-            m.p = 0.0
-
-
-def _train_step(model, x, y, aux):
-    from segmentron.solver.loss import MixSoftmaxCrossEntropyLoss
-    model.train()
-    model.zero_grad()
-    outs = model(x)
-    loss = MixSoftmaxCrossEntropyLoss(aux=aux, aux_weight=0.4, ignore_index=-1)(outs, y)["loss"]
-    loss.backward()
-    return loss, outs
-
-
-def main(os32=False):
+def main():
     import numpy as np
     import torch
     import _bisenet_oracle as O
-    from oracle import ref_import, synth
-    over = ["MODEL.OUTPUT_STRIDE", "32", "SOLVER.AUX", "False"] if os32 else ["SOLVER.AUX", "True"]
-    model, _ = ref_import.build_reference_model(YAML, over)
-    keys = [(k, list(v.shape)) for k, v in model.state_dict().items()]
-    sd = O.state([(k, tuple(s)) for k, s in keys])
-    model.load_state_dict(sd)
-    _no_dropout(model)
-    if os32:
+    from oracle import synth
+    args = G.parse_args(__doc__, leg="os32")
+    out = args.out
+    over = ["MODEL.OUTPUT_STRIDE", "32", "SOLVER.AUX", "False"] if args.os32 \
+        else ["SOLVER.AUX", "True"]
+    model, keys, sd = G.reference_model(O, YAML, over)
+    if args.os32:
         x = synth.synth_images(O.B_TRAIN, O.H32, O.W32, seed=0)
         y = synth.synth_targets(O.B_TRAIN, O.H32, O.W32, seed=0)
-        loss, outs = _train_step(model, x, y, aux=False)
-        np.savez_compressed(os.path.join(GOLDEN, "bisenet_os32_train.npz"),
+        loss, outs = G.train_step(model, x, y, aux=False)
+        np.savez_compressed(os.path.join(out, "bisenet_os32_train.npz"),
                             loss=np.float64(loss.item()),
                             logits0=outs[0].detach().numpy()[..., ::2, ::2])
         print("OS 32: loss %.6f" % loss.item())
         return
-    n_params = sum(p.numel() for p in model.parameters())
-    with open(os.path.join(GOLDEN, "bisenet_state_keys.json"), "w") as f:
-        json.dump({"config": YAML, "keys": keys, "n_params": n_params}, f)
-    shutil.copyfile(os.path.join(ref_import.REFERENCE_ROOT, YAML),
-                    os.path.join(GOLDEN, os.path.basename(YAML)))
-    print("%d keys, %d parameters" % (len(keys), n_params))
+    G.write_schema(out, "bisenet", YAML, model, keys)
     # evaluation, running statistics as synthesised
     model.eval()
     with torch.no_grad():
         ev = model(synth.synth_images(O.B_EVAL, O.H, O.W, seed=0))
-    np.savez_compressed(os.path.join(GOLDEN, "bisenet_eval.npz"), logits0=ev[0].numpy())
+    np.savez_compressed(os.path.join(out, "bisenet_eval.npz"), logits0=ev[0].numpy())
     # one training step: float64 first (the yardstick of the float32 run), then float32
     x = synth.synth_images(O.B_TRAIN, O.H, O.W, seed=0)
     y = synth.synth_targets(O.B_TRAIN, O.H, O.W, seed=0)
     model.double()
-    loss64, outs64 = _train_step(model, x.double(), y, aux=True)
-    g64 = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+    loss64, outs64 = G.train_step(model, x.double(), y, aux=True)
+    g64 = G.grads_of(model)
     model.float()
     model.load_state_dict(sd)
-    loss, outs = _train_step(model, x, y, aux=True)
-    g32 = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+    loss, outs = G.train_step(model, x, y, aux=True)
+    g32 = G.grads_of(model)
     num = sum((g32[k].double() - g64[k]).pow(2).sum().item() for k in g64) ** 0.5
     den = sum(g64[k].pow(2).sum().item() for k in g64) ** 0.5
     worst = max((g32[k].double() - g64[k]).norm().item() / max(g64[k].norm().item(), 1e-30)
@@ -108,13 +82,11 @@ def main(os32=False):
         arrs["logits%d" % i] = o.detach().numpy()[..., ::step, ::step]
     for k, g in g32.items():
         arrs["gnorm::" + k] = np.float64(g.double().norm().item())
-    for k, v in model.state_dict().items():
-        if "running_" in k or k.endswith("num_batches_tracked"):
-            arrs["stat::" + k] = v.numpy()
-    np.savez_compressed(os.path.join(GOLDEN, "bisenet_train.npz"), **arrs)
+    arrs.update(G.stats_of(model))
+    np.savez_compressed(os.path.join(out, "bisenet_train.npz"), **arrs)
     print("training step: loss %.6f" % loss.item())
-    subprocess.check_call([sys.executable, os.path.abspath(__file__), "--os32"])
+    subprocess.check_call([sys.executable, os.path.abspath(__file__), "--os32", "--out", out])
 
 
 if __name__ == "__main__":
-    main(os32="--os32" in sys.argv[1:])
+    main()

@@ -20,146 +20,56 @@ tests/_cgnet_oracle.py (oracle.synth seed 0, conditioned; PReLU slopes in [0.05,
                                          few-sample BatchNorm path (768 / 192 rows)
 
 Before anything is written the float32 run is compared with the reference in float64: the float32
-run must itself satisfy the gradient acceptance rule of tests/test_cgnet_gpu.py with the margin that
-rule grants the device (err_cpu32 := 0): global error <= 1e-4, at most 10 % of the tensors beyond
-1e-3 relative and none beyond 3e-2.
+run must itself satisfy the gradient acceptance rule of tests/_zoo.py (check_gradients) with the
+margin that rule grants the device (err_cpu32 := 0): global error <= 1e-4, at most 10 % of the
+tensors beyond 1e-3 relative and none beyond 3e-2.
 
-    python tools/gen_golden_cgnet.py       (the small leg runs in a second process: the
-                                            reference's cfg is a frozen per-process singleton)
+    python tools/gen_golden_cgnet.py [--out DIR]   (the small leg runs in a second process: the
+                                                    reference's cfg is a frozen per-process
+                                                    singleton)
 """
-import json
 import os
-import shutil
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
+import _golden_zoo as G
+
 YAML = "configs/cityscapes_cgnet.yaml"
 
 
-def _no_dropout(model):
-    import torch.nn as nn
-    for m in model.modules():
-        if isinstance(m, (nn.Dropout, nn.Dropout2d)):
-            m.p = 0.0
-
-
-def _train_step(model, x, y):
-    from segmentron.solver.loss import MixSoftmaxCrossEntropyLoss
-    model.train()
-    model.zero_grad()
-    outs = model(x)
-    loss = MixSoftmaxCrossEntropyLoss(aux=False, ignore_index=-1)(outs, y)["loss"]
-    loss.backward()
-    return loss, outs
-
-
-def _train_fixture(model, sd, b, h, w, check):
-    """-> arrays of one training step of the reference (float32, checked against its float64
-    run) on synth images / targets of b x 3 x h x w."""
-    import numpy as np
-    import torch
-    from oracle import synth
-    x = synth.synth_images(b, h, w, seed=0)
-    y = synth.synth_targets(b, h, w, seed=0)
-    model.double()
-    model.load_state_dict({k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()})
-    loss64, outs64 = _train_step(model, x.double(), y)
-    g64 = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
-    model.float()
-    model.load_state_dict(sd)
-    loss, outs = _train_step(model, x, y)
-    g32 = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
-    assert set(g32) == set(k for k, _ in model.named_parameters()), "parameter without gradient"
-    err = {k: (g32[k].double() - g64[k]).norm().item() for k in g64}
-    nrm = {k: g64[k].norm().item() for k in g64}
-    num = sum(e * e for e in err.values()) ** 0.5
-    den = sum(n * n for n in nrm.values()) ** 0.5
-    worst = max(err[k] / max(nrm[k], 1e-30) for k in g64)
-    lerr = (outs[0].double() - outs64[0]).abs().max().item() / outs64[0].abs().max().item()
-    print("%d x %d x %d float32 vs float64: loss %.2e, logits %.2e, gradient global %.2e, worst "
-          "tensor %.2e" % (b, h, w, abs(loss.item() - loss64.item()) / loss64.item(), lerr,
-                           num / den, worst))
-    if check:
-        # the acceptance rule of tests/test_cgnet_gpu.py on the reference's own float32 run
-        over = [k for k in g64 if err[k] > 1e-3 * nrm[k]]
-        print("tensors beyond 1e-3 relative in the reference's float32 run: %d of %d"
-              % (len(over), len(g64)))
-        assert num / den <= 1e-4, "fixture is not well conditioned: re-condition the state"
-        assert len(over) <= 0.1 * len(g64) and all(err[k] <= 3e-2 * nrm[k] for k in over), \
-            "fixture is not well conditioned: re-condition the state"
-    arrs = {"loss": np.float64(loss.item()), "cpu::grad_global": np.float64(num / den),
-            "logits0": outs[0].detach().numpy()[..., ::2, ::2]}
-    for k, g in g32.items():
-        arrs["gnorm::" + k] = np.float64(g.double().norm().item())
-        arrs["gerr32::" + k] = np.float64(err[k])
-    for k, v in model.state_dict().items():
-        if "running_" in k or k.endswith("num_batches_tracked"):
-            arrs["stat::" + k] = v.numpy()
-    print("training step: loss %.6f" % loss.item())
-    return arrs, x, y
-
-
-def main(small=False):
+def main():
     import numpy as np
     import torch
     import _cgnet_oracle as O
-    from oracle import ref_import, synth
-    model, _ = ref_import.build_reference_model(YAML, O.SMALL_OVERRIDES if small else [])
-    keys = [(k, list(v.shape)) for k, v in model.state_dict().items()]
-    sd = O.state([(k, tuple(s)) for k, s in keys])
-    model.load_state_dict(sd)
-    _no_dropout(model)
-    if small:
+    from oracle import synth
+    args = G.parse_args(__doc__, leg="small")
+    out = args.out
+    model, keys, sd = G.reference_model(O, YAML, O.SMALL_OVERRIDES if args.small else [])
+    if args.small:
         assert (len(model.stage2), len(model.stage3)) == (1, 1)
-        arrs, _, _ = _train_fixture(model, sd, O.B, O.H, O.W, check=False)
-        np.savez_compressed(os.path.join(GOLDEN, "cgnet_small_train.npz"), **arrs)
+        arrs, _, _ = G._train_fixture(model, sd, O.B, O.H, O.W, check=False)
+        np.savez_compressed(os.path.join(out, "cgnet_small_train.npz"), **arrs)
         return
-    n_params = sum(p.numel() for p in model.parameters())
-    with open(os.path.join(GOLDEN, "cgnet_state_keys.json"), "w") as f:
-        json.dump({"config": YAML, "keys": keys, "n_params": n_params,
-                   "decoder": list(model.decoder)}, f)
-    shutil.copyfile(os.path.join(ref_import.REFERENCE_ROOT, YAML),
-                    os.path.join(GOLDEN, os.path.basename(YAML)))
-    print("%d keys, %d parameters" % (len(keys), n_params))
+    G.write_schema(out, "cgnet", YAML, model, keys, decoder=list(model.decoder))
     # evaluation, running statistics as synthesised
     model.eval()
     with torch.no_grad():
         ev = model(synth.synth_images(O.B, O.H, O.W, seed=0))
         odd = model(synth.synth_images(1, O.H_ODD, O.W_ODD, seed=0))
-    np.savez_compressed(os.path.join(GOLDEN, "cgnet_eval.npz"),
+    np.savez_compressed(os.path.join(out, "cgnet_eval.npz"),
                         logits0=ev[0].numpy()[..., ::2, ::2],
                         shape_odd=np.array(odd[0].shape, dtype=np.int64),
                         n_outputs=np.int64(len(ev)))
     print("eval: %d outputs, %s; odd input -> %s" % (len(ev), tuple(ev[0].shape),
                                                       tuple(odd[0].shape)))
-    arrs, x, y = _train_fixture(model, sd, O.TB, O.TH, O.TW, check=True)
-    # the float64-checked restatement under CPU bfloat16 autocast: the bf16 bars
-    l64, _, og64, _ = O.train(sd, x, y, dtype=torch.float64)
-    lbf, _, ogbf, _ = O.train(sd, x, y, autocast=True)
-    dot = sum((ogbf[k].double() * og64[k]).sum().item() for k in og64)
-    na = sum(ogbf[k].double().pow(2).sum().item() for k in og64) ** 0.5
-    nb = sum(og64[k].pow(2).sum().item() for k in og64) ** 0.5
-    bf_loss, bf_cos = abs(lbf - l64) / abs(l64), dot / (na * nb)
-    print("CPU bf16 autocast vs float64: loss %.4e relative, gradient cosine %.6f"
-          % (bf_loss, bf_cos))
-    arrs["cpu::bf16_loss_rel"] = np.float64(bf_loss)
-    arrs["cpu::bf16_grad_cos"] = np.float64(bf_cos)
-    logits = arrs.pop("logits0")
-    half = logits.shape[0] // 2
-    np.savez_compressed(os.path.join(GOLDEN, "cgnet_train.npz"), **arrs)
-    np.savez_compressed(os.path.join(GOLDEN, "cgnet_train_logits_a.npz"), logits0=logits[:half])
-    np.savez_compressed(os.path.join(GOLDEN, "cgnet_train_logits_b.npz"), logits0=logits[half:])
-    subprocess.check_call([sys.executable, os.path.abspath(__file__), "--small"])
-    for f in ("cgnet_state_keys.json", "cgnet_eval.npz", "cgnet_train.npz",
-              "cgnet_train_logits_a.npz", "cgnet_train_logits_b.npz", "cgnet_small_train.npz"):
-        size = os.path.getsize(os.path.join(GOLDEN, f))
-        print("%s: %d bytes" % (f, size))
-        assert size < (1 << 20), f
+    arrs, x, y = G._train_fixture(model, sd, O.TB, O.TH, O.TW, check=True)
+    arrs.update(G.bf16_yardstick(O, sd, x, y))
+    G.save_train(out, "cgnet", arrs)
+    subprocess.check_call([sys.executable, os.path.abspath(__file__), "--small", "--out", out])
+    G.assert_sizes(out, ("cgnet_state_keys.json", "cgnet_eval.npz", "cgnet_train.npz",
+                         "cgnet_train_logits_a.npz", "cgnet_train_logits_b.npz",
+                         "cgnet_small_train.npz"))
 
 
 if __name__ == "__main__":
-    main(small="--small" in sys.argv[1:])
+    main()

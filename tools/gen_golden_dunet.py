@@ -23,73 +23,46 @@ tests/_dunet_oracle.py (oracle.synth seed 0, conditioned):
 
 Before anything is written the float32 run is compared with the reference in float64: global
 gradient error <= 1e-4, worst tensor <= 5e-4, and the float32 run must itself satisfy the
-per-tensor acceptance rule of tests/test_dunet_gpu.py with the margin that rule grants the device.
+per-tensor acceptance rule of tests/_zoo.py (check_gradients) with the margin that rule grants the
+device.
 
-    python tools/gen_golden_dunet.py            (the OS 16 leg runs in a second process: the
-                                                 reference's cfg is a frozen per-process singleton)
+    python tools/gen_golden_dunet.py [--out DIR]     (the OS 16 leg runs in a second process: the
+                                                      reference's cfg is a frozen per-process
+                                                      singleton)
 """
-import json
 import os
-import shutil
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
+import _golden_zoo as G
+
 YAML = "configs/cityscapes_dunet.yaml"
 
 
-def _no_dropout(model):
-    import torch.nn as nn
-    for m in model.modules():
-        if isinstance(m, nn.Dropout):
-            m.p = 0.0
-
-
-def _train_step(model, x, y):
-    from segmentron.solver.loss import MixSoftmaxCrossEntropyLoss
-    model.train()
-    model.zero_grad()
-    outs = model(x)
-    loss = MixSoftmaxCrossEntropyLoss(aux=True, aux_weight=0.4, ignore_index=-1)(outs, y)["loss"]
-    loss.backward()
-    return loss, outs
-
-
-def main(os16=False):
+def main():
     import numpy as np
     import torch
     import _dunet_oracle as O
-    from oracle import ref_import, synth
-    over = ["SOLVER.AUX", "True"] + (["MODEL.OUTPUT_STRIDE", "16"] if os16 else [])
-    model, _ = ref_import.build_reference_model(YAML, over)
-    keys = [(k, list(v.shape)) for k, v in model.state_dict().items()]
-    sd = O.state([(k, tuple(s)) for k, s in keys])
-    model.load_state_dict(sd)
-    _no_dropout(model)
-    if os16:
+    from oracle import synth
+    args = G.parse_args(__doc__, leg="os16")
+    out = args.out
+    over = ["SOLVER.AUX", "True"] + (["MODEL.OUTPUT_STRIDE", "16"] if args.os16 else [])
+    model, keys, sd = G.reference_model(O, YAML, over)
+    if args.os16:
         model.eval()
         with torch.no_grad():
             ev = model(synth.synth_images(O.B, O.H, O.W, seed=0))
-        np.savez_compressed(os.path.join(GOLDEN, "dunet_os16_eval.npz"),
+        np.savez_compressed(os.path.join(out, "dunet_os16_eval.npz"),
                             logits0=ev[0].numpy(), logits1=ev[1].numpy())
         print("OS 16 eval: %s" % (tuple(ev[0].shape),))
         return
-    n_params = sum(p.numel() for p in model.parameters())
-    with open(os.path.join(GOLDEN, "dunet_state_keys.json"), "w") as f:
-        json.dump({"config": YAML, "keys": keys, "n_params": n_params,
-                   "decoder": list(model.decoder)}, f)
-    shutil.copyfile(os.path.join(ref_import.REFERENCE_ROOT, YAML),
-                    os.path.join(GOLDEN, os.path.basename(YAML)))
-    print("%d keys, %d parameters" % (len(keys), n_params))
+    G.write_schema(out, "dunet", YAML, model, keys, decoder=list(model.decoder))
     # evaluation, running statistics as synthesised
     model.eval()
     with torch.no_grad():
         ev = model(synth.synth_images(O.B, O.H, O.W, seed=0))
         odd = model(synth.synth_images(1, O.H_ODD, O.W_ODD, seed=0))
-    np.savez_compressed(os.path.join(GOLDEN, "dunet_eval.npz"),
+    np.savez_compressed(os.path.join(out, "dunet_eval.npz"),
                         logits0=ev[0].numpy()[..., ::2, ::2],
                         shape_odd=np.array(odd[0].shape, dtype=np.int64),
                         n_outputs=np.int64(len(ev)))
@@ -100,12 +73,12 @@ def main(os16=False):
     y = synth.synth_targets(O.B, O.H, O.W, seed=0)
     print("targets: %.1f %% ignored" % (100.0 * (y == -1).float().mean().item()))
     model.double()
-    loss64, outs64 = _train_step(model, x.double(), y)
-    g64 = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+    loss64, outs64 = G.train_step(model, x.double(), y, aux=True)
+    g64 = G.grads_of(model)
     model.float()
     model.load_state_dict(sd)
-    loss, outs = _train_step(model, x, y)
-    g32 = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+    loss, outs = G.train_step(model, x, y, aux=True)
+    g32 = G.grads_of(model)
     err = {k: (g32[k].double() - g64[k]).norm().item() for k in g64}
     nrm = {k: g64[k].norm().item() for k in g64}
     num = sum(e * e for e in err.values()) ** 0.5
@@ -122,40 +95,26 @@ def main(os16=False):
     print("float32 vs float64: loss %.2e, logits %.2e, gradient global %.2e, worst tensor %.2e"
           % (abs(loss.item() - loss64.item()) / loss64.item(), lerr, num / den, worst))
     assert num / den <= 1e-4 and worst <= 5e-4, "fixture is not well conditioned"
-    # the acceptance rule of tests/test_dunet_gpu.py, applied to the reference's own float32 run
-    # with err_cpu32 := 0 (the strictest reading): at most 10 % of the tensors beyond 1e-3
+    # the acceptance rule of tests/_zoo.py check_gradients, applied to the reference's own float32
+    # run with err_cpu32 := 0 (the strictest reading): at most 10 % of the tensors beyond 1e-3
     over = [k for k in g64 if err[k] > 1e-3 * nrm[k]]
     print("tensors beyond 1e-3 relative in the reference's float32 run: %d of %d"
           % (len(over), len(g64)))
     assert len(over) <= 0.1 * len(g64), "choose another seed"
-    # the float64-checked restatement under CPU bfloat16 autocast: the bf16 bars
-    l64, _, og64, _ = O.train(sd, x, y, dtype=torch.float64)
-    lbf, _, ogbf, _ = O.train(sd, x, y, autocast=True)
-    dot = sum((ogbf[k].double() * og64[k]).sum().item() for k in og64)
-    na = sum(ogbf[k].double().pow(2).sum().item() for k in og64) ** 0.5
-    nb = sum(og64[k].pow(2).sum().item() for k in og64) ** 0.5
-    bf_loss, bf_cos = abs(lbf - l64) / abs(l64), dot / (na * nb)
-    print("CPU bf16 autocast vs float64: loss %.4e relative, gradient cosine %.6f"
-          % (bf_loss, bf_cos))
-    arrs = {"loss": np.float64(loss.item()), "cpu::bf16_loss_rel": np.float64(bf_loss),
-            "cpu::bf16_grad_cos": np.float64(bf_cos), "cpu::grad_global": np.float64(num / den)}
+    arrs = {"loss": np.float64(loss.item()), "cpu::grad_global": np.float64(num / den)}
+    arrs.update(G.bf16_yardstick(O, sd, x, y))
     for i, o in enumerate(outs):
         arrs["logits%d" % i] = o.detach().numpy()[..., ::2, ::2]  # (1 MiB per committed file)
     for k, g in g32.items():
         arrs["gnorm::" + k] = np.float64(g.double().norm().item())
         arrs["gerr32::" + k] = np.float64(err[k])
-    for k, v in model.state_dict().items():
-        if "running_" in k or k.endswith("num_batches_tracked"):
-            arrs["stat::" + k] = v.numpy()
-    np.savez_compressed(os.path.join(GOLDEN, "dunet_train.npz"), **arrs)
+    arrs.update(G.stats_of(model))
+    np.savez_compressed(os.path.join(out, "dunet_train.npz"), **arrs)
     print("training step: loss %.6f" % loss.item())
-    subprocess.check_call([sys.executable, os.path.abspath(__file__), "--os16"])
-    for f in ("dunet_state_keys.json", "dunet_eval.npz", "dunet_train.npz",
-              "dunet_os16_eval.npz"):
-        size = os.path.getsize(os.path.join(GOLDEN, f))
-        print("%s: %d bytes" % (f, size))
-        assert size < (1 << 20), f
+    subprocess.check_call([sys.executable, os.path.abspath(__file__), "--os16", "--out", out])
+    G.assert_sizes(out, ("dunet_state_keys.json", "dunet_eval.npz", "dunet_train.npz",
+                         "dunet_os16_eval.npz"))
 
 
 if __name__ == "__main__":
-    main(os16="--os16" in sys.argv[1:])
+    main()

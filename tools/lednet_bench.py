@@ -28,20 +28,15 @@ Weights and inputs are synthesised; timings do not depend on them."""
 import argparse
 import json
 import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import _bench_zoo as Z
 
 # N, H, W, C (one branch: half of the block's channels), dilations
 LINE_SHAPES = [(4, 384, 384, 16, (1,)), (4, 192, 192, 32, (1,)), (4, 96, 96, 64, (1, 2, 5, 9, 17))]
 TAIL_SHAPES = [(4, 384, 384, 32), (4, 192, 192, 64), (4, 96, 96, 128)]
 TRAIN_SHAPE = (4, 768, 768)
-LEG_TIMEOUT = 420  # seconds per child
+TRAIN = {"yaml": "cityscapes_lednet.yaml", "shape": TRAIN_SHAPE, "aux_weight": 0.4}
 
 
 def _with_rates(res, nbytes):
@@ -53,7 +48,6 @@ def _with_rates(res, nbytes):
 def line_leg(iters, repeats):
     import torch
     import torch.nn.functional as TF
-    from cgnet_bench import _measure
     from segmentron_amd import functional as F
     from segmentron_amd import hip_ops as K
     torch.backends.cudnn.enabled = False
@@ -92,7 +86,7 @@ def line_leg(iters, repeats):
                     "aten_wgrad": lambda: bwd((False, True, False))[1],
                 }
                 key = "%dx%dx%dx%d/%s/d%d" % (N, H, W, C, "HW"[axis], d)
-                out[key] = _with_rates(_measure(variants, iters, repeats), nbytes)
+                out[key] = _with_rates(Z.measure(variants, iters, repeats), nbytes)
                 sys.stderr.write("%s %s\n" % (key, json.dumps(out[key])))
     return out
 
@@ -104,7 +98,6 @@ def _shuffle(x):
 
 def tail_leg(iters, repeats):
     import torch
-    from cgnet_bench import _measure
     from segmentron_amd import hip_ops as K
     dt = torch.bfloat16
     out = {}
@@ -139,27 +132,11 @@ def tail_leg(iters, repeats):
             "aten_fwd": aten_fwd,
             "aten_fwdbwd": aten_fwd_bwd,
         }
-        r = _measure(variants, iters, repeats)
+        r = Z.measure(variants, iters, repeats)
         r["hip_fwd"]["GB_per_s"] = round(3 * elems / (r["hip_fwd"]["median_us"] * 1e-6) / 1e9, 1)
         r["hip_bwd"]["GB_per_s"] = round(3 * elems / (r["hip_bwd"]["median_us"] * 1e-6) / 1e9, 1)
         out["%dx%dx%dx%d" % (N, H, W, C)] = r
     return out
-
-
-def _model(dtype, phase="train"):
-    import segmentron_amd
-    from oracle import synth
-    from segmentron_amd.config import cfg, reset_cfg
-    reset_cfg()
-    cfg.update_from_file(os.path.join(ROOT, "tests", "golden", "cityscapes_lednet.yaml"))
-    cfg.update_from_list(["TRAIN.BACKBONE_PRETRAINED", "False"])
-    cfg.PHASE = phase
-    cfg.check_and_freeze()
-    segmentron_amd.set_compute_dtype(dtype)
-    model = segmentron_amd.get_segmentation_model()
-    sd = synth.synth_like(model.state_dict(), seed=0, conditioned=True)
-    model.load_state_dict(sd)
-    return model.cuda().train(), sd
 
 
 def launches_leg():
@@ -168,7 +145,7 @@ def launches_leg():
     import torch
     from torch.profiler import ProfilerActivity, profile
     os.environ["SEGMENTRON_HIP_GRAPH"] = "0"
-    model, _ = _model(torch.bfloat16)
+    model, _ = Z.build_model(TRAIN["yaml"], torch.bfloat16)
     block = model.encoder[10]
     x = torch.randn(4, 96, 96, 128, device="cuda").to(torch.bfloat16).relu_().requires_grad_()
     go = torch.randn(4, 96, 96, 128, device="cuda").to(torch.bfloat16)
@@ -194,66 +171,6 @@ def launches_leg():
     return names
 
 
-def train_leg(dtype, steps, warmup, graph):
-    import torch
-    import torch.nn as nn
-    from oracle import synth
-    from segmentron_amd.config import reset_cfg
-    from segmentron_amd.solver.optimizer import get_optimizer
-    os.environ["SEGMENTRON_HIP_GRAPH"] = "1" if graph else "0"
-    model, _ = _model(dtype)
-    crit = nn.CrossEntropyLoss(ignore_index=-1)
-    optimizer = get_optimizer(model)
-    B, H, W = TRAIN_SHAPE
-    x = synth.synth_images(B, H, W, seed=0).cuda()
-    y = synth.synth_targets(B, H, W, seed=0).cuda()
-
-    def step():
-        outputs = model(x)
-        loss = crit(outputs[0], y)
-        optimizer.zero_grad()
-        loss.backward()
-        optimizer.step()
-        return loss
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        loss = step()
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) * 1e3 / steps
-    if graph:
-        tg = model._transparent_graph
-        assert tg.disabled is None and len(tg.segments) == 1, tg.disabled
-    assert torch.isfinite(loss)
-    reset_cfg()
-    return {"ms_per_step": round(ms, 3), "img_per_s": round(B * 1e3 / ms, 2)}
-
-
-def train_aten_leg(steps, warmup):
-    """The torch restatement on torch's own device kernels, float32 parameters under bf16
-    autocast: forward + cross-entropy + backward (no optimizer step)."""
-    import torch
-    import _lednet_oracle as O
-    from oracle import synth
-    from test_lednet import fixture_keys
-    torch.backends.cudnn.enabled = False
-    sd = {k: v.cuda() for k, v in O.state(fixture_keys()[1]).items()}
-    B, H, W = TRAIN_SHAPE
-    x = synth.synth_images(B, H, W, seed=0).cuda()
-    y = synth.synth_targets(B, H, W, seed=0).cuda()
-    for _ in range(warmup):
-        O.train(sd, x, y, autocast=True)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        O.train(sd, x, y, autocast=True)
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) * 1e3 / steps
-    return {"ms_per_step": round(ms, 3), "img_per_s": round(B * 1e3 / ms, 2)}
-
-
 def child(args):
     import torch
     if args.leg == "line":
@@ -263,11 +180,12 @@ def child(args):
     elif args.leg == "launches":
         val = launches_leg()
     elif args.leg == "train_aten":
-        val = train_aten_leg(args.steps, args.warmup)
+        from _zoo import LEDNET
+        val = Z.train_aten_leg(LEDNET, TRAIN_SHAPE, args.steps, args.warmup)
     else:
-        val = train_leg(torch.bfloat16, args.steps, args.warmup, graph=args.leg == "train_graph")
-    print("RESULT " + json.dumps({"leg": args.leg, "value": val,
-                                  "device": torch.cuda.get_device_name(0)}))
+        val = Z.train_leg(TRAIN, torch.bfloat16, args.steps, args.warmup,
+                          graph=args.leg == "train_graph")
+    Z.emit_result(val)
 
 
 def main():
@@ -282,33 +200,11 @@ def main():
     args = ap.parse_args()
     if args.leg:
         return child(args)
-    res = {"line_shapes": LINE_SHAPES, "tail_shapes": TAIL_SHAPES, "train_shape": TRAIN_SHAPE,
-           "dtype": "bf16", "steps": args.steps, "warmup": args.warmup, "iters": args.iters,
-           "repeats": args.repeats, "results": {}}
-    for leg in args.legs.split(","):
-        cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--steps", str(args.steps),
-               "--warmup", str(args.warmup), "--iters", str(args.iters), "--repeats",
-               str(args.repeats)]
-        try:
-            p = subprocess.run(cmd, capture_output=True, text=True, timeout=LEG_TIMEOUT)
-        except subprocess.TimeoutExpired:
-            sys.stderr.write("leg %s ran past %d s: stopping\n" % (leg, LEG_TIMEOUT))
-            return 124
-        line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
-        if p.returncode != 0 or not line:  # nothing more is started on the GPU
-            sys.stderr.write("leg %s failed (%d): stopping\n%s\n" % (leg, p.returncode,
-                                                                     p.stderr[-3000:]))
-            return p.returncode or 1
-        r = json.loads(line[0][len("RESULT "):])
-        res["device"] = r["device"]
-        res["results"][leg] = r["value"]
-        sys.stderr.write("%s: %s\n" % (leg, json.dumps(r["value"])))
-    text = json.dumps(res)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    return 0
+    header = {"line_shapes": LINE_SHAPES, "tail_shapes": TAIL_SHAPES, "train_shape": TRAIN_SHAPE,
+              "dtype": "bf16", "steps": args.steps, "warmup": args.warmup, "iters": args.iters,
+              "repeats": args.repeats}
+    legs = [(leg, ["--leg", leg]) for leg in args.legs.split(",")]
+    return Z.run_legs(__file__, legs, args, header, passed=("steps", "warmup", "iters", "repeats"))
 
 
 if __name__ == "__main__":

@@ -17,7 +17,8 @@ import argparse
 import json
 import os
 import sys
-import time
+
+from _bench_zoo import timed
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -51,18 +52,6 @@ def loss_of(name, out, y):
                       align_corners=False).squeeze_(1).long()
     return TF.cross_entropy(pred, y, ignore_index=-1) + \
         TF.cross_entropy(out["rend"], gt, ignore_index=-1)
-
-
-def timed(fn, steps, warmup):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / steps
 
 
 def main():
