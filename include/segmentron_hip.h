@@ -710,7 +710,20 @@ int seg_fold_bwd_finalize_sync(void* p2p, const float* dsdt, int rows, const dou
  *   seg_conv_line_wgrad: partial fp32 [splits][O][C][3] (splits from seg_conv_line_wgrad_splits;
  *                        the memory layout of the [O,C,3,1] / [O,C,1,3] parameter itself),
  *                        dW[o][c][t] = sum_p dy[p][o] * act(x)[p + tap t][c]; sum with seg_colsum.
- * No atomics, fixed summation order: every launch is bit-identical.                            */
+ * No atomics, fixed summation order: every launch is bit-identical.
+ * C == O == 40 (EDANet's EDABlock, segmentron/models/edanet.py:107-116) is served on packed or
+ * pitched 40-channel tensors (no padding: in bf16 the void upper half of the third 16-channel
+ * k-step is masked in registers; the weight packing stays [O][3*C] with C = 40) by the
+ * seg_conv_line_bias_* entries and the weight gradient.  seg_conv_line_ok / _geom / _fwd keep the
+ * classes they have always had and refuse C = 40.
+ *   seg_conv_line_bias_ok / _geom: the queries above for C in {16, 32, 40, 64}
+ *   seg_conv_line_bias_fwd: seg_conv_line_fwd with a per-channel float32 bias [C] (nullable),
+ *                        added to the accumulators BEFORE add, the rounding and the statistics;
+ *                        the zero padding of a consumer applies after it.  With the data
+ *                        gradient's weights and stat_partial, row sums [.][0][c] are the
+ *                        per-channel sums of dx as stored: the bias gradient of a biased
+ *                        producer convolution that feeds x directly.
+ *                        For C in {16, 32, 64} seg_conv_line_fwd is this call with bias = NULL.  */
 int seg_conv_line_ok(int dtype, int C, int axis, int dil);
 int seg_conv_line_geom(int dtype, int N, int H, int W, int C, int what);
 int seg_conv_line_wgrad_splits(int dtype, int N, int H, int W, int C);
@@ -718,6 +731,12 @@ int seg_conv_line_fwd(int dtype, const void* x, long ldx, int N, int H, int W, i
                       const void* wp, int axis, int dil, int pro_mode, const float* pro_scale,
                       const float* pro_shift, void* y, long ldy, const void* add, long ldadd,
                       float* stat_partial, void* stream);
+int seg_conv_line_bias_ok(int dtype, int C, int axis, int dil);
+int seg_conv_line_bias_geom(int dtype, int N, int H, int W, int C, int what);
+int seg_conv_line_bias_fwd(int dtype, const void* x, long ldx, int N, int H, int W, int C,
+                           const void* wp, const float* bias, int axis, int dil, int pro_mode,
+                           const float* pro_scale, const float* pro_shift, void* y, long ldy,
+                           const void* add, long ldadd, float* stat_partial, void* stream);
 int seg_conv_line_wgrad(int dtype, const void* x, long ldx, const void* dy, long lddy, int N,
                         int H, int W, int C, int axis, int dil, int pro_mode,
                         const float* pro_scale, const float* pro_shift, float* partial, int splits,
@@ -733,6 +752,44 @@ int seg_ssnbt_tail_fwd(int dtype, const void* y0, long ldy0, const float* s0, co
                        long ldx, void* out, long ldout, long P, int C, void* stream);
 int seg_ssnbt_tail_bwd(int dtype, const void* gout, long ldgout, const void* out, long ldout,
                        void* gm, long ldgm, long P, int C, void* stream);
+
+/* ---- EDANet: a pair of line convolutions in one launch (csrc/conv_line_pair.hip) ---------------
+ * EDABlock runs its line convolutions as conv3x1 -> conv1x3 with only the first bias in between
+ * (segmentron/models/edanet.py:127-128, 132-133).  C == O == 40, one dilation for both:
+ *   mid = lineA(act(x)) + bias_a  (rounded to `dtype` as a store rounds it)
+ *   y   = lineB(mid) + bias_b (+ add)
+ * order 0: (A, B) = (H, W), order 1: (W, H).  One block owns one whole line along B (a row / a
+ * column) and keeps its `mid` in LDS; a tap of stage B outside the line is zero AFTER bias_a.
+ * wa / wb: the [O][3*C] packings of seg_conv_line_fwd.  mid (nullable): also stored to global
+ * memory.  stat_partial (nullable): fp32 [rows][2][C] of y as stored; mid_sums (nullable): fp32
+ * [rows][C] per-channel sums of mid as stored; rows = seg_conv_line_pair_rows.  y and mid are
+ * bit-identical to two seg_conv_line_bias_fwd launches; no atomics, fixed summation order.
+ * The data gradient of an order-0 pair is the order-1 pair on dy with the weights repacked
+ * [C][2-t][O] (B's first) and no biases: its mid is d mid, its mid_sums are d bias_a.
+ *   seg_conv_line_pair_ok  : 1 if (dtype, C, line length L along B, dil) is served: C == 40 and
+ *                            the weights of both convolutions + L * (C * sizeof + 16) bytes of
+ *                            `mid` fit 64 KB of LDS (L <= 436 in bf16, 136 in float32); pure
+ *                            host query
+ *   seg_conv_line_pair_rows: blocks = rows of stat_partial / mid_sums; -1 on bad input          */
+int seg_conv_line_pair_ok(int dtype, int C, int L, int dil);
+int seg_conv_line_pair_rows(int N, int H, int W, int order);
+int seg_conv_line_pair_fwd(int dtype, const void* x, long ldx, int N, int H, int W, int C,
+                           const void* wa, const float* bias_a, const void* wb,
+                           const float* bias_b, int order, int dil, int pro_mode,
+                           const float* pro_scale, const float* pro_shift, void* mid, long ldmid,
+                           void* y, long ldy, const void* add, long ldadd, float* stat_partial,
+                           float* mid_sums, void* stream);
+
+/* ---- EDANet: channel placement for the down-sampler's concat (csrc/edanet.hip) ----------------
+ * DownsamplerBlock (segmentron/models/edanet.py:90-97) concatenates a stride-2 convolution with a
+ * 2x2 max-pool of its input at channel offsets (12, 45) that are no whole 16-byte vector.
+ *   dst[p][c] = c < C ? src[p][c] : 0   for p < P, c < Cz  (C <= Cz <= 4096)
+ * element-wise, any channel alignment; src and dst are already offset to their first channel and
+ * have their own row pitches (lds >= C, ldd >= Cz).  Forward: the pooled channels into their
+ * slice of the concat buffer (Cz = C); backward: that slice of the gradient into an aligned
+ * tensor of the pool's width with zeros in its pad channels (Cz > C).                          */
+int seg_chan_copy(int dtype, const void* src, long lds, void* dst, long ldd, long P, int C,
+                  int Cz, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,12 +4,18 @@
 //   y[n,h,w,o] = sum_{t=0..2} sum_c act(x[n, h + (t-1)*d*[axis==H], w + (t-1)*d*[axis==W], c])
 //                                   * wp[o][t][c]                   (+ add[n,h,w,o], nullable)
 //
-// C == O in {16, 32, 64}: K = 3C = 48 .. 192 and O <= 64 leave the implicit GEMM's 128x128 tiles
+// C == O in {16, 32, 40, 64}: K = 3C = 48 .. 192 and O <= 64 leave the implicit GEMM's 128x128 tile
 // mostly empty and pay LDS staging for an operand that needs none: one MFMA B fragment of a lane
 // IS one 16-byte channel vector of one pixel at one tap.  So, as in conv3x3_direct.hip, A = the
 // weights (bf16: in registers for the kernel's lifetime, at most 96 VGPRs; float32: in LDS) and
 // B = pixels straight from global memory / L2; a lane ends up with 4 consecutive output channels
 // of ONE pixel (32x32 C/D map of conv_gemm.h).  O = 16 leaves the upper 16 MFMA rows zero.
+// C = 40 (EDANet's growth rate): no padded tensors.  In bf16 a k-step is 16 channels, so the upper
+// half of the third step (channels 40..47) is masked to zero in registers on both operands and its
+// loads are clamped to the lane's own vector; output rows 40..63 of the second 32-row group are
+// zero weights and are never stored.  A nullable per-channel float32 bias is added to the
+// accumulators BEFORE `add`, the rounding and the statistics; a consumer's zero padding applies
+// after it.
 //
 // A wave owns 32 consecutive pixels of the flattened [N*H*W] index per tile, a block 4 waves =
 // CL_TILE pixels; blocks are persistent and walk a contiguous, XCD-local range of tiles.  A tap
@@ -32,6 +38,7 @@ struct LineArgs {
   const void* add; long ldadd;
   const float* ps; const float* pt; int pro_mode;
   float* stat;
+  const float* bias;  // nullable, [C]
   int H, W, axis, d;  // axis 0: H (3x1 kernel), 1: W (1x3)
   int P, ntiles;
 };
@@ -45,7 +52,9 @@ __device__ __forceinline__ int line_pos(const LineArgs& a, int p) {
 template <typename T, int C> struct LineGeom {
   static constexpr int VEC = Vec<T>::N;
   static constexpr int KSTEP = 2 * VEC;  // k per vector step: 16 (bf16) / 8 (f32)
-  static constexpr int KS = C / KSTEP;
+  static constexpr int KS = (C + KSTEP - 1) / KSTEP;
+  static constexpr bool KTAIL = C % KSTEP != 0;  // C = 40, bf16: the last step's upper half is void
+  static_assert(C % VEC == 0, "whole channel vectors");
   static constexpr int NOG = (C + 31) / 32;
   static constexpr bool WREG = sizeof(T) == 2;
   static constexpr int WPITCH = 3 * C * (int)sizeof(T) + 16;  // LDS weight row (f32 only)
@@ -78,8 +87,11 @@ __global__ __launch_bounds__(CL_THREADS) void conv_line_kernel(const LineArgs a)
 #pragma unroll
       for (int t = 0; t < 3; ++t)
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-          wf[og][t][ks] = mask_u4(ldg16(wrow + t * C + ks * G::KSTEP), orow);
+        for (int ks = 0; ks < KS; ++ks) {
+          const bool kv = !G::KTAIL || ks * G::KSTEP + h * VEC < C;
+          wf[og][t][ks] =
+              mask_u4(ldg16(wrow + t * C + (kv ? ks * G::KSTEP : -h * VEC)), orow && kv);
+        }
     }
   } else {
     constexpr int VPR = 3 * C / VEC;
@@ -122,7 +134,10 @@ __global__ __launch_bounds__(CL_THREADS) void conv_line_kernel(const LineArgs a)
 #pragma unroll
     for (int t = 0; t < 3; ++t)
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) raw[t][ks] = ldg16(X + off[t] + ks * G::KSTEP);
+      for (int ks = 0; ks < KS; ++ks) {
+        const bool kv = !G::KTAIL || ks * G::KSTEP + h * VEC < C;
+        raw[t][ks] = ldg16(X + off[t] + (kv ? ks * G::KSTEP : -h * VEC));
+      }
 
     f32x16 acc[NOG];
 #pragma unroll
@@ -131,8 +146,9 @@ __global__ __launch_bounds__(CL_THREADS) void conv_line_kernel(const LineArgs a)
       for (int e = 0; e < 16; ++e) acc[og][e] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
+      const bool kv = !G::KTAIL || ks * G::KSTEP + h * VEC < C;
       float ps[VEC], pt[VEC];
-      if (PRO && (a.pro_mode & PRO_AFFINE)) {
+      if (PRO && (a.pro_mode & PRO_AFFINE) && kv) {
         load_params<VEC>(a.ps, ks * G::KSTEP + h * VEC, ps);
         load_params<VEC>(a.pt, ks * G::KSTEP + h * VEC, pt);
       } else {
@@ -148,7 +164,7 @@ __global__ __launch_bounds__(CL_THREADS) void conv_line_kernel(const LineArgs a)
           apply_prologue_regs<VEC>(f, a.pro_mode, ps, pt);
           b = Vec<T>::pack(f);
         }
-        b = mask_u4(b, ok[t]);
+        b = mask_u4(b, G::KTAIL ? (ok[t] && kv) : ok[t]);
 #pragma unroll
         for (int og = 0; og < NOG; ++og) {
           uint4 wv;
@@ -175,6 +191,12 @@ __global__ __launch_bounds__(CL_THREADS) void conv_line_kernel(const LineArgs a)
       for (int g = 0; g < 4; ++g) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) f[g][j] = acc[og][g * 4 + j];
+        if (g < gv && a.bias != nullptr) {
+          float bv[4];
+          load_params<4>(a.bias, og * 32 + g * 8 + h * 4, bv);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) f[g][j] += bv[j];
+        }
         if (g < gv && A != nullptr) {
           const T* ap = A + (long)p * a.ldadd + og * 32 + g * 8 + h * 4;
           float av[4];
@@ -199,7 +221,7 @@ __global__ __launch_bounds__(CL_THREADS) void conv_line_kernel(const LineArgs a)
           uint2 recv;
           recv.x = __shfl_xor(send.x, 32, 64);
           recv.y = __shfl_xor(send.y, 32, 64);
-          if (gp < gv && pv) {
+          if (gp + h < gv && pv) {
             const uint2 own = h ? pk[gp + 1] : pk[gp];
             const uint4 v = h ? make_uint4(recv.x, recv.y, own.x, own.y)
                               : make_uint4(own.x, own.y, recv.x, recv.y);
@@ -268,8 +290,8 @@ __global__ __launch_bounds__(CL_THREADS) void conv_line_kernel(const LineArgs a)
 // ds_read_b64_tr_b16 (as conv3x3_direct.hip's weight gradient), float32 element-wise for
 // v_mfma_f32_32x32x2_f32.  The three taps share the dy fragment.  C <= 32: one [32 o][32 c] tile
 // per tap, the 4 waves split the trip's pixels and are summed through LDS in wave order at the
-// end; C = 64: wave w owns output half w & 1 and input half w >> 1.  One fp32 partial [O][C][3]
-// per block, summed by seg_colsum.
+// end; C = 40 (staged as 64) and 64: wave w owns output half w & 1 and input half w >> 1.  One
+// fp32 partial [O][C][3] per block, summed by seg_colsum.
 typedef __attribute__((address_space(3))) unsigned char cl_lds_t;
 typedef short cl_v4i16 __attribute__((ext_vector_type(4)));
 typedef short cl_v8i16 __attribute__((ext_vector_type(8)));
@@ -293,9 +315,11 @@ struct LineWgradArgs {
 
 template <typename T, int C> struct LineWGeom {
   static constexpr int VEC = Vec<T>::N;
-  // pixels per staging trip (float32 at C = 64: 32, to stay inside 64 KB of LDS)
-  static constexpr int TP = (sizeof(T) == 4 && C == 64) ? 32 : 64;
-  static constexpr int CP = C < 32 ? 32 : C;  // staged channels per pixel (C = 16: upper half 0)
+  // staged channels per pixel: whole 32-channel MFMA tiles (C = 16: upper half 0; C = 40:
+  // channels 40..63 are 0 and their products are not stored)
+  static constexpr int CP = (C + 31) / 32 * 32;
+  // pixels per staging trip (float32 at 64 staged channels: 32, to stay inside 64 KB of LDS)
+  static constexpr int TP = (sizeof(T) == 4 && CP == 64) ? 32 : 64;
   static constexpr int NG = CP / 32;
   static constexpr bool KSPLIT = NG == 1;
   static constexpr int PITCH = CP * (int)sizeof(T) + 16;
@@ -445,7 +469,8 @@ __global__ __launch_bounds__(CL_THREADS) void conv_line_wgrad_kernel(const LineW
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int o = og * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        Pp[(long)o * (3 * C) + (cg * 32 + r32) * 3 + t] = acc[t][e];
+        if (G::CP == C || (o < C && cg * 32 + r32 < C))
+          Pp[(long)o * (3 * C) + (cg * 32 + r32) * 3 + t] = acc[t][e];
       }
   }
 }
@@ -530,9 +555,15 @@ __global__ __launch_bounds__(ST_THREADS) void ssnbt_tail_bwd_kernel(const TailAr
 }
 
 // ---------------------------------------------------------------------------------------------
+// what seg_conv_line_ok / _geom / _fwd have always served ...
 static bool line_ok(int dtype, int C, int axis, int dil) {
   return (dtype == DT_F32 || dtype == DT_BF16) && (C == 16 || C == 32 || C == 64) &&
          (axis == 0 || axis == 1) && dil >= 1 && dil < (1 << 20);
+}
+
+// ... and what the seg_conv_line_bias_* entries and the weight gradient serve: C = 40 as well
+static bool line_bias_ok(int dtype, int C, int axis, int dil) {
+  return C == 40 ? line_ok(dtype, 32, axis, dil) : line_ok(dtype, C, axis, dil);
 }
 
 static int line_grid(long P) {
@@ -540,9 +571,9 @@ static int line_grid(long P) {
   return (int)(nt < CL_MAX_BLOCKS ? nt : CL_MAX_BLOCKS);
 }
 
-static int line_wgrad_cap(int C) { return C == 64 ? 128 : (C == 32 ? 512 : 1024); }
+static int line_wgrad_cap(int C) { return C > 32 ? 128 : (C == 32 ? 512 : 1024); }
 
-static int line_wgrad_tp(int dtype, int C) { return dtype == DT_F32 && C == 64 ? 32 : 64; }
+static int line_wgrad_tp(int dtype, int C) { return dtype == DT_F32 && C > 32 ? 32 : 64; }
 
 static int line_wgrad_grid(int dtype, long P, int C) {
   const int tp = line_wgrad_tp(dtype, C);
@@ -586,10 +617,12 @@ static void launch_line_wgrad(const LineWgradArgs& a, int grid, hipStream_t s) {
     if (dtype == DT_BF16) {                                     \
       if (C == 16) fn<bf16_t, 16>(__VA_ARGS__);                 \
       else if (C == 32) fn<bf16_t, 32>(__VA_ARGS__);            \
+      else if (C == 40) fn<bf16_t, 40>(__VA_ARGS__);            \
       else fn<bf16_t, 64>(__VA_ARGS__);                         \
     } else {                                                    \
       if (C == 16) fn<float, 16>(__VA_ARGS__);                  \
       else if (C == 32) fn<float, 32>(__VA_ARGS__);             \
+      else if (C == 40) fn<float, 40>(__VA_ARGS__);             \
       else fn<float, 64>(__VA_ARGS__);                          \
     }                                                           \
   } while (0)
@@ -598,12 +631,17 @@ extern "C" int seg_conv_line_ok(int dtype, int C, int axis, int dil) {
   return seg::line_ok(dtype, C, axis, dil) ? 1 : 0;
 }
 
+extern "C" int seg_conv_line_bias_ok(int dtype, int C, int axis, int dil) {
+  return seg::line_bias_ok(dtype, C, axis, dil) ? 1 : 0;
+}
+
 // what: 0 pixels per tile, 1 grid (= rows of stat_partial), 2 tiles per block,
 //       3 pixels per trip of the weight gradient
-extern "C" int seg_conv_line_geom(int dtype, int N, int H, int W, int C, int what) {
+extern "C" int seg_conv_line_bias_geom(int dtype, int N, int H, int W, int C, int what) {
   using namespace seg;
   const long P = (long)N * H * W;
-  if (!line_ok(dtype, C, 0, 1) || N < 1 || H < 1 || W < 1 || P >= (1L << 31) - CL_TILE) return -1;
+  if (!line_bias_ok(dtype, C, 0, 1) || N < 1 || H < 1 || W < 1 || P >= (1L << 31) - CL_TILE)
+    return -1;
   const int grid = line_grid(P);
   const long nt = (P + CL_TILE - 1) / CL_TILE;
   switch (what) {
@@ -615,20 +653,26 @@ extern "C" int seg_conv_line_geom(int dtype, int N, int H, int W, int C, int wha
   }
 }
 
+extern "C" int seg_conv_line_geom(int dtype, int N, int H, int W, int C, int what) {
+  return seg::line_ok(dtype, C, 0, 1) ? seg_conv_line_bias_geom(dtype, N, H, W, C, what) : -1;
+}
+
 extern "C" int seg_conv_line_wgrad_splits(int dtype, int N, int H, int W, int C) {
   using namespace seg;
   const long P = (long)N * H * W;
-  if (!line_ok(dtype, C, 0, 1) || N < 1 || H < 1 || W < 1 || P >= (1L << 31) - CL_TILE) return -1;
+  if (!line_bias_ok(dtype, C, 0, 1) || N < 1 || H < 1 || W < 1 || P >= (1L << 31) - CL_TILE)
+    return -1;
   return line_wgrad_grid(dtype, P, C);
 }
 
-extern "C" int seg_conv_line_fwd(int dtype, const void* x, long ldx, int N, int H, int W, int C,
-                                 const void* wp, int axis, int dil, int pro_mode,
-                                 const float* pro_scale, const float* pro_shift, void* y, long ldy,
-                                 const void* add, long ldadd, float* stat_partial, void* stream) {
+extern "C" int seg_conv_line_bias_fwd(int dtype, const void* x, long ldx, int N, int H, int W, int C,
+                                      const void* wp, const float* bias, int axis, int dil,
+                                      int pro_mode, const float* pro_scale, const float* pro_shift,
+                                      void* y, long ldy, const void* add, long ldadd,
+                                      float* stat_partial, void* stream) {
   using namespace seg;
-  SEG_REQUIRE(line_ok(dtype, C, axis, dil), "conv_line_fwd: unsupported dtype %d C %d axis %d dil %d",
-              dtype, C, axis, dil);
+  SEG_REQUIRE(line_bias_ok(dtype, C, axis, dil),
+              "conv_line_bias_fwd: unsupported dtype %d C %d axis %d dil %d", dtype, C, axis, dil);
   const long P = (long)N * H * W;
   SEG_REQUIRE(N >= 1 && H >= 1 && W >= 1 && P < (1L << 31) - CL_TILE, "conv_line_fwd: bad shape");
   const int vec = dtype == DT_BF16 ? 8 : 4;
@@ -642,6 +686,7 @@ extern "C" int seg_conv_line_fwd(int dtype, const void* x, long ldx, int N, int 
   LineArgs a;
   a.x = x; a.ldx = ldx; a.w = wp; a.y = y; a.ldy = ldy; a.add = add; a.ldadd = ldadd;
   a.ps = pro_scale; a.pt = pro_shift; a.pro_mode = pro_mode; a.stat = stat_partial;
+  a.bias = bias;
   a.H = H; a.W = W; a.axis = axis; a.d = dil; a.P = (int)P;
   a.ntiles = (int)((P + CL_TILE - 1) / CL_TILE);
   const int grid = line_grid(P);
@@ -649,12 +694,24 @@ extern "C" int seg_conv_line_fwd(int dtype, const void* x, long ldx, int N, int 
   return check_launch("conv_line_fwd");
 }
 
+extern "C" int seg_conv_line_fwd(int dtype, const void* x, long ldx, int N, int H, int W, int C,
+                                 const void* wp, int axis, int dil, int pro_mode,
+                                 const float* pro_scale, const float* pro_shift, void* y, long ldy,
+                                 const void* add, long ldadd, float* stat_partial, void* stream) {
+  // (this entry keeps the classes it has always had; C = 40 is the bias entry's)
+  SEG_REQUIRE(seg::line_ok(dtype, C, axis, dil),
+              "conv_line_fwd: unsupported dtype %d C %d axis %d dil %d", dtype, C, axis, dil);
+  return seg_conv_line_bias_fwd(dtype, x, ldx, N, H, W, C, wp, nullptr, axis, dil, pro_mode,
+                                pro_scale, pro_shift, y, ldy, add, ldadd, stat_partial, stream);
+}
+
 extern "C" int seg_conv_line_wgrad(int dtype, const void* x, long ldx, const void* dy, long lddy,
                                    int N, int H, int W, int C, int axis, int dil, int pro_mode,
                                    const float* pro_scale, const float* pro_shift, float* partial,
                                    int splits, void* stream) {
   using namespace seg;
-  SEG_REQUIRE(line_ok(dtype, C, axis, dil), "conv_line_wgrad: unsupported dtype %d C %d axis %d dil %d",
+  SEG_REQUIRE(line_bias_ok(dtype, C, axis, dil),
+              "conv_line_wgrad: unsupported dtype %d C %d axis %d dil %d",
               dtype, C, axis, dil);
   const long P = (long)N * H * W;
   SEG_REQUIRE(N >= 1 && H >= 1 && W >= 1 && P < (1L << 31) - CL_TILE, "conv_line_wgrad: bad shape");

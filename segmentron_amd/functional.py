@@ -646,13 +646,19 @@ class _ConvFn(torch.autograd.Function):
             res = None
             if s.fork is not None and s.fork.g is not None:
                 res = s.fork.take()  # the identity path's gradient of a forked block input
+            # (a DenseGrad's gradient is a channel suffix of the stage's gradient buffer, of the
+            # input's padded width: the GEMM adds into it IN PLACE — every thread reads the
+            # addend element it then stores)
+            inplace = res is not None and getattr(s.fork, "inplace", False) \
+                and tuple(res.shape) == tuple(x.shape) and _sum_n_operand_ok(res, K.vec_of(dt))
             if s.stride == 1 and res is not None and KH == 1 and KW == 1 and s.bn_in is None \
-                    and not s.relu and Cx == Cw and Cw % K.vec_of(dt) == 0 and res.dtype == dt:
+                    and not s.relu and (Cx == Cw or inplace) and Cx % K.vec_of(dt) == 0 \
+                    and res.dtype == dt:
                 # ... rides in the data-gradient GEMM's store path: the epilogue's
                 # y = acc - c0 - c1 * x with c0 = 0, c1 = -1 (ResNet bottlenecks, resnet.py:52-79:
                 # 33 element-wise adds of 135 MB tensors per PSPNet step, 2.4 of 72 ms)
-                g, _ = K.conv_gemm(dy_full, wt, Cw, 1, 1, 1, 0, 1,
-                                   ep=(res, _const(Cw, x.device, 0.0), _const(Cw, x.device, -1.0)))
+                g, _ = K.conv_gemm(dy_full, wt, Cx, 1, 1, 1, 0, 1, out=res if inplace else None,
+                                   ep=(res, _const(Cx, x.device, 0.0), _const(Cx, x.device, -1.0)))
                 res = None
             elif s.stride == 1:
                 g, _ = K.conv_gemm(dy_full, wt, Cx, KH, KW, 1, s.dil * (KH - 1) - s.pad, s.dil)
@@ -2374,42 +2380,63 @@ def split_halves(x, bg):
 
 def _line_geometry(conv):
     """(axis, dilation) of a factorised nn.Conv2d: kernel (3,1) -> K.AXIS_H, (1,3) -> K.AXIS_W;
-    stride 1, padding = dilation along that axis only, no bias, C == O."""
+    stride 1, padding = dilation along that axis only, C == O (a bias is fine: see
+    line_conv_bn).  The dilation of the OTHER axis has no tap to act on: EDANet's
+    nn.Conv2d(k, k, (3, 1), padding=(d, 0), dilation=d) (edanet.py:114) is dilation (d, d)."""
     ks = tuple(conv.kernel_size)
     if ks not in ((3, 1), (1, 3)):
         raise NotImplementedError("line_conv_bn: kernel_size %s is not (3,1) / (1,3)" % (ks,))
     axis = K.AXIS_H if ks == (3, 1) else K.AXIS_W
     d = conv.dilation[axis]
-    if (conv.groups != 1 or conv.bias is not None or tuple(conv.stride) != (1, 1)
+    if (conv.groups != 1 or tuple(conv.stride) != (1, 1)
             or conv.padding[axis] != d or conv.padding[1 - axis] != 0
-            or conv.dilation[1 - axis] != 1 or conv.in_channels != conv.out_channels
+            or conv.in_channels != conv.out_channels
             or conv.padding_mode != "zeros"):
         raise NotImplementedError("line_conv_bn: %r is not a dense same-size 3-tap convolution "
-                                  "without bias" % (conv,))
+                                  "with as many outputs as inputs" % (conv,))
     return axis, d
 
 
+class LineBias:
+    """Hand-off of the bias gradient of the FIRST convolution of a line pair (EDABlock:
+    conv3x1 -> conv1x3 with nothing but the bias in between, edanet.py:127-128).  That gradient is
+    the per-channel sum of the gradient with respect to `mid`, which the second convolution's
+    data-gradient launch produces — and sums, as stored, in its statistics rows.  The second
+    convolution (line_conv_bn(mid_of=)) leaves the rows here; the first (bias_grad=) folds them."""
+    __slots__ = ("partial",)
+
+    def __init__(self):
+        self.partial = None
+
+
 class LineSpec:
-    def __init__(self, act, axis, dil, out, want_stats, first, half):
+    def __init__(self, act, axis, dil, out, want_stats, first, half, drop_bias=False,
+                 bias_grad=None, mid_of=None):
         self.bn_in, self.relu, self.pro = act.bn, act.relu, act.pro
         self.axis, self.dil, self.out, self.want_stats = axis, dil, out, want_stats
         self.first, self.half = first, half
+        self.drop_bias, self.bias_grad, self.mid_of = drop_bias, bias_grad, mid_of
         self.partial = None
 
 
 class _LineConvFn(torch.autograd.Function):
     """nn.Conv2d (3,1) / (1,3) on a deferred activation: csrc/conv_line.hip.  The data gradient is
     the same kernel on dy with the weights repacked [C][2-t][O]; the weight gradient re-applies the
-    forward prologue."""
+    forward prologue.  A bias in front of a training-mode BatchNorm is left out of the stored
+    tensor (spec.drop_bias, as _ConvFn: its gradient is an exact zero); otherwise the kernel adds
+    it, and its gradient is the column sum of dy — taken from the statistics rows of the
+    consumer's data-gradient launch where that consumer is the pair's second convolution."""
 
     @staticmethod
-    def forward(ctx, x, in_gamma, in_beta, weight, spec):
+    def forward(ctx, x, in_gamma, in_beta, weight, bias, spec):
         C, dt = x.shape[-1], x.dtype
         wp = cached_pack(weight, ("fwd", C, dt), lambda: pack_conv_weight(weight, C, dt))
-        y, spec.partial = K.conv_line(x, wp, spec.axis, spec.dil, spec.pro, out=spec.out,
-                                      want_stats=spec.want_stats)
+        b = None if bias is None or spec.drop_bias else bias.detach()
+        y, spec.partial = K.conv_line_bias(x, wp, b, spec.axis, spec.dil, spec.pro, out=spec.out,
+                                           want_stats=spec.want_stats)
         spec.out = None  # (it IS y: see _ConvFn)
         ctx.spec = spec
+        ctx.has_bias = bias is not None
         ctx.save_for_backward(x, weight)
         return y
 
@@ -2421,6 +2448,17 @@ class _LineConvFn(torch.autograd.Function):
         if dy.dtype != dt or not _sum_n_operand_ok(dy, K.vec_of(dt)):
             dy = dy.to(dt).contiguous()
         dW = K.conv_line_wgrad(x, dy, s.axis, s.dil, s.pro).view(weight.shape)
+        dbias = None
+        if ctx.has_bias and s.drop_bias:
+            dbias = torch.zeros(C, dtype=torch.float32, device=dy.device)
+        elif ctx.has_bias:
+            rows = None
+            if s.bias_grad is not None:
+                rows, s.bias_grad.partial = s.bias_grad.partial, None
+            if rows is not None:  # sums of dy as the consumer's data-gradient launch stored it
+                dbias = K.colsum(rows.view(rows.shape[0], 2 * C), f64=False)[:C]
+            else:
+                dbias = K.bn_bwd_reduce(dy, dy, (PRO_NONE, None, None))[:C].float()
         dx = dgamma = dbeta = None
         if ctx.needs_input_grad[0]:
             wt = cached_pack(weight, ("dgrad", C, dt, C),
@@ -2432,35 +2470,160 @@ class _LineConvFn(torch.autograd.Function):
                     bg.dx = torch.empty((N, H, W, 2 * C), dtype=dt, device=x.device)
                 sl = slice(s.half * C, (s.half + 1) * C)
                 add = bg.gm[..., sl] if bg.gm is not None else None
-                dx, _ = K.conv_line(dy, wt, s.axis, s.dil, out=bg.dx[..., sl], add=add)
+                dx, _ = K.conv_line_bias(dy, wt, None, s.axis, s.dil, out=bg.dx[..., sl], add=add)
                 bg.added[s.half] = add is not None
             else:
-                g, _ = K.conv_line(dy, wt, s.axis, s.dil)
+                give = s.mid_of is not None and s.bn_in is None and not s.relu
+                g, rows = K.conv_line_bias(dy, wt, None, s.axis, s.dil, want_stats=give)
+                if give:
+                    s.mid_of.partial = rows
                 dx, dgamma, dbeta = bn_input_backward(g, x, s.bn_in, s.relu, inplace=True)
-        return dx, dgamma, dbeta, dW, None
+        return dx, dgamma, dbeta, dW, dbias, None
 
 
-def line_conv_bn(act, conv, bn=None, out=None, first=None, half=0):
+def line_conv_bn(act, conv, bn=None, out=None, first=None, half=0, bias_grad=None, mid_of=None):
     """Factorised 3-tap conv (nn.Conv2d (3,1) / (1,3), see _line_geometry) [+ BatchNorm
     statistics] -> an Act whose BN (if any) is pending; the caller sets ``.relu``.  `first`: the
     BlockGrad of the SSnbt block whose input half `half` (0 / 1) this convolution reads — its
-    input must be plain."""
+    input must be plain.  A biased convolution in front of a training-mode BatchNorm behaves as
+    conv_bn's: the bias stays out of the stored tensor, enters the running mean and has an exact
+    zero gradient; in front of anything else the kernel adds it.  `bias_grad` / `mid_of`: the
+    LineBias shared by the first / second convolution of a pair (see there)."""
     axis, d = _line_geometry(conv)
     x = act.t
-    if not K.conv_line_ok(x.dtype, x.shape[-1], axis, d) or x.shape[-1] != conv.in_channels:
+    if not K.conv_line_bias_ok(x.dtype, x.shape[-1], axis, d) or x.shape[-1] != conv.in_channels:
         raise NotImplementedError("line_conv_bn: no kernel for %s with %d channels at dilation %d"
                                   % (x.dtype, x.shape[-1], d))
     if is_group_norm(bn):
         raise NotImplementedError("line_conv_bn: GroupNorm is not served here")
     if first is not None and (act.bn is not None or act.relu):
         raise ValueError("line_conv_bn: the first convolution of a block reads its plain input")
-    spec = LineSpec(act, axis, d, out, bn is not None and uses_batch_stats(bn), first, half)
+    batch_stats = bn is not None and uses_batch_stats(bn)
+    drop_bias = batch_stats and conv.bias is not None
+    spec = LineSpec(act, axis, d, out, batch_stats, first, half, drop_bias, bias_grad, mid_of)
     g, b = act.params
-    y = _LineConvFn.apply(x, g, b, conv.weight, spec)
+    y = _LineConvFn.apply(x, g, b, conv.weight, conv.bias, spec)
     if bn is None:
         return Act(y)
     N, H, W, _ = y.shape
-    return Act(y, finish_bn(bn, spec.partial, N * H * W, y=y))
+    return Act(y, finish_bn(bn, spec.partial, N * H * W,
+                            conv.bias.detach() if drop_bias else None, y=y))
+
+
+def _pair_measured_faster(dtype, L, dil, order, want_mid):
+    """The classes on which the pair kernel measured faster than the two launches, in-graph, by
+    more than the spread of the replays (profiles/edanet.md, bf16 only): order (H, W) with `mid`
+    kept in LDS alone (no backward pass follows), on 256-pixel lines (30.6 against 33.5 us at
+    [4,128,256]) or at dilation 16 (11.8 against 12.8 us at [4,64,128]).  With `mid` written it
+    ties at dilation 1 / 2, in order (W, H) it loses everywhere (a block's pixels are a whole
+    row apart), and the graphed train step does not move (8.61 against 8.57 - 8.62 ms)."""
+    return dtype == torch.bfloat16 and order == 0 and not want_mid and (L >= 256 or dil >= 16)
+
+
+def line_pair_routed(dtype, C, L, dil, order=0, want_mid=True):
+    """Does line_pair_bn run a pair of axis order `order` (0: (H, W), 1: (W, H)) with lines of L
+    pixels along its SECOND axis as one launch (csrc/conv_line_pair.hip)?  SEG_LINE_PAIR=0 forces
+    the two launches everywhere, SEG_LINE_PAIR=1 the pair wherever the kernel can run (A/B timing,
+    the equality tests); unset: only the classes where it measured faster."""
+    mode = os.environ.get("SEG_LINE_PAIR")
+    if mode == "0" or not K.conv_line_pair_ok(dtype, C, L, dil):
+        return False
+    return mode == "1" or _pair_measured_faster(dtype, L, dil, order, want_mid)
+
+
+class PairSpec:
+    def __init__(self, act, order, dil, out, want_stats, drop_bias_b):
+        self.bn_in, self.relu, self.pro = act.bn, act.relu, act.pro
+        self.order, self.dil, self.out, self.want_stats = order, dil, out, want_stats
+        self.drop_bias_b = drop_bias_b
+        self.want_mid = torch.is_grad_enabled()
+        self.partial = None
+
+
+class _LinePairFn(torch.autograd.Function):
+    """convA (3,1) / (1,3) -> convB on the other axis, both biased, as ONE launch
+    (seg_conv_line_pair_fwd); `mid` goes to global memory only where a backward pass may follow.
+    Backward: the data gradient is the pair kernel again, on dy with the axes swapped and the
+    weights repacked — its `mid` is d mid, the operand of the first weight gradient, and its mid
+    sums are the first bias gradient — where that geometry is routed, else two single launches."""
+
+    @staticmethod
+    def forward(ctx, x, in_gamma, in_beta, wa, ba, wb, bb, spec):
+        C, dt = x.shape[-1], x.dtype
+        pa = cached_pack(wa, ("fwd", C, dt), lambda: pack_conv_weight(wa, C, dt))
+        pb = cached_pack(wb, ("fwd", C, dt), lambda: pack_conv_weight(wb, C, dt))
+        y, mid, spec.partial, _ = K.conv_line_pair(
+            x, pa, None if ba is None else ba.detach(), pb,
+            None if bb is None or spec.drop_bias_b else bb.detach(), spec.order, spec.dil,
+            spec.pro, out=spec.out, want_mid=spec.want_mid, want_stats=spec.want_stats)
+        spec.out = None  # (it IS y: see _ConvFn)
+        ctx.spec = spec
+        ctx.has_bias = (ba is not None, bb is not None)
+        ctx.save_for_backward(x, mid, wa, wb)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mid, wa, wb = ctx.saved_tensors
+        s = ctx.spec
+        N, H, W, C = x.shape
+        dt = x.dtype
+        if dy.dtype != dt or not _sum_n_operand_ok(dy, K.vec_of(dt)):
+            dy = dy.to(dt).contiguous()
+        axis_a, axis_b = (K.AXIS_H, K.AXIS_W) if s.order == 0 else (K.AXIS_W, K.AXIS_H)
+        dWb = K.conv_line_wgrad(mid, dy, axis_b, s.dil).view(wb.shape)
+        dbb = None
+        if ctx.has_bias[1] and s.drop_bias_b:
+            dbb = torch.zeros(C, dtype=torch.float32, device=dy.device)
+        elif ctx.has_bias[1]:
+            dbb = K.bn_bwd_reduce(dy, dy, (PRO_NONE, None, None))[:C].float()
+        ta = cached_pack(wa, ("dgrad", C, dt, C), lambda: pack_conv_weight_dgrad(wa, C, dt))
+        tb = cached_pack(wb, ("dgrad", C, dt, C), lambda: pack_conv_weight_dgrad(wb, C, dt))
+        want_dx = ctx.needs_input_grad[0]
+        if want_dx and line_pair_routed(dt, C, W if s.order == 1 else H, s.dil, 1 - s.order):
+            g, dmid, _, sums = K.conv_line_pair(dy, tb, None, ta, None, 1 - s.order, s.dil,
+                                                want_mid=True, want_mid_sums=True)
+            dba = K.colsum(sums, f64=False)
+        else:
+            dmid, rows = K.conv_line_bias(dy, tb, None, axis_b, s.dil, want_stats=True)
+            dba = K.colsum(rows.view(rows.shape[0], 2 * C), f64=False)[:C]
+            g = K.conv_line_bias(dmid, ta, None, axis_a, s.dil)[0] if want_dx else None
+        dWa = K.conv_line_wgrad(x, dmid, axis_a, s.dil, s.pro).view(wa.shape)
+        dx = dgamma = dbeta = None
+        if want_dx:
+            dx, dgamma, dbeta = bn_input_backward(g, x, s.bn_in, s.relu, inplace=True)
+        return dx, dgamma, dbeta, dWa, (dba if ctx.has_bias[0] else None), dWb, dbb, None
+
+
+def line_pair_bn(act, conv_a, conv_b, bn=None, out=None):
+    """conv_a -> conv_b, two factorised 3-tap convolutions on different axes with equal dilation
+    and nothing but conv_a's bias in between (EDABlock), [+ BatchNorm statistics] -> an Act as
+    from line_conv_bn.  One launch where line_pair_routed says so, else two line_conv_bn calls
+    (whose first bias gradient comes from the second data-gradient launch: LineBias)."""
+    axis_a, d = _line_geometry(conv_a)
+    axis_b, d_b = _line_geometry(conv_b)
+    if axis_a == axis_b or d != d_b or conv_a.in_channels != conv_b.in_channels:
+        raise NotImplementedError("line_pair_bn: %r, %r is not a (3,1) / (1,3) pair of one "
+                                  "dilation and width" % (conv_a, conv_b))
+    if is_group_norm(bn):
+        raise NotImplementedError("line_pair_bn: GroupNorm is not served here")
+    x = act.t
+    N, H, W, C = x.shape
+    order = 0 if axis_a == K.AXIS_H else 1
+    if C != conv_a.in_channels or not line_pair_routed(x.dtype, C, W if order == 0 else H, d, order,
+                                                      torch.is_grad_enabled()):
+        lb = LineBias()
+        mid = line_conv_bn(act, conv_a, None, bias_grad=lb)
+        return line_conv_bn(mid, conv_b, bn, out=out, mid_of=lb)
+    batch_stats = bn is not None and uses_batch_stats(bn)
+    drop_b = batch_stats and conv_b.bias is not None
+    spec = PairSpec(act, order, d, out, batch_stats, drop_b)
+    g, b = act.params
+    y = _LinePairFn.apply(x, g, b, conv_a.weight, conv_a.bias, conv_b.weight, conv_b.bias, spec)
+    if bn is None:
+        return Act(y)
+    return Act(y, finish_bn(bn, spec.partial, N * H * W,
+                            conv_b.bias.detach() if drop_b else None, y=y))
 
 
 class TailSpec:
@@ -2511,6 +2674,84 @@ def ssnbt_tail(a0, a1, x, bg=None, out=None):
     g0, b0 = a0.params
     g1, b1 = a1.params
     return _SSnbtTailFn.apply(a0.t, g0, b0, a1.t, g1, b1, x, TailSpec(a0, a1, bg, out))
+
+
+# ---- EDANet: dense blocks in one buffer, the down-sampler's concat (models/edanet.py) -----------
+class DenseGrad(GradFork):
+    """Hand-off of the gradient of a dense block's input (EDABlock: `cat([new, x], 1)`,
+    edanet.py:140).  The stage keeps ONE gradient buffer with the layout of its activation
+    buffer; the block's `dense_cat` backward parks the channel suffix that belongs to x here
+    (kind POST) and the block's 1x1 convolution — x's only other consumer, which autograd runs
+    later — adds its data-gradient product into that suffix in place, in the GEMM's epilogue
+    (`_ConvFn.backward`), and returns it.  No slice backward, no zero-fill, no element-wise add."""
+    __slots__ = ()
+    inplace = True
+
+    def __init__(self):
+        super().__init__(GradFork.POST)
+
+
+class _DenseCatFn(torch.autograd.Function):
+    """cat([new, prev], channel) where both already lie in `buf`, `new` directly in front of
+    `prev`: returns the suffix view buf[..., lo:].  Backward hands `new` its own slice of the
+    gradient and parks the rest in the DenseGrad (see there); without one, or where the 1x1
+    convolution takes no part in the backward pass, `prev` gets its slice view as from _CatFn."""
+
+    @staticmethod
+    def forward(ctx, new, prev, buf, lo, dg):
+        ctx.k, ctx.dg = new.shape[-1], dg
+        ctx.set_materialize_grads(False)
+        return buf[..., lo:]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None
+        k, dg = ctx.k, ctx.dg
+        gn, gp = g[..., :k], g[..., k:]
+        if dg is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] \
+                and dg.g is None and not dg.closed:
+            dg.g = gp
+            return gn, None, None, None, None
+        return (gn if ctx.needs_input_grad[0] else None), \
+            (gp if ctx.needs_input_grad[1] else None), None, None, None
+
+
+def dense_cat(new, prev, buf, lo, dg=None):
+    """new = buf[..., lo:lo+k] and prev = buf[..., lo+k:] (both written) -> buf[..., lo:] as one
+    autograd node.  dg: the DenseGrad shared with the 1x1 convolution that reads `prev`
+    (conv_bn(fork=dg))."""
+    k = new.shape[-1]
+    if new.data_ptr() != buf[..., lo:].data_ptr() \
+            or prev.data_ptr() != buf[..., lo + k:].data_ptr() \
+            or prev.shape[-1] != buf.shape[-1] - lo - k:
+        raise ValueError("dense_cat: new / prev are not buf[..., lo:lo+k] / buf[..., lo+k:]")
+    if not (torch.is_grad_enabled() and (new.requires_grad or prev.requires_grad)):
+        return buf[..., lo:]
+    return _DenseCatFn.apply(new, prev, buf, lo, dg)
+
+
+class _PlaceFn(torch.autograd.Function):
+    """The first C channels of `src` written into `spec[0]`, a C-channel slice of a concat buffer
+    at ANY channel offset (seg_chan_copy).  Backward: that slice of the gradient, re-aligned to
+    src's width with zeros behind C."""
+
+    @staticmethod
+    def forward(ctx, src, C, spec):
+        ctx.C, ctx.width = C, src.shape[-1]
+        return K.chan_copy(src, spec.pop(), C)
+
+    @staticmethod
+    def backward(ctx, g):
+        N, H, W, _ = g.shape
+        gs = torch.empty((N, H, W, ctx.width), dtype=g.dtype, device=g.device)
+        return K.chan_copy(g, gs, ctx.C), None, None
+
+
+def place(src, C, out):
+    """src[..., :C] -> out (a C-channel slice of a concat buffer whose offset need not be a
+    whole channel vector: EDANet's DownsamplerBlock, cat([conv 45, pool 15]))."""
+    return _PlaceFn.apply(src, C, [out])
 
 
 def max_pool(act, k, stride, pad):

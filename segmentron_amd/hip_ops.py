@@ -1631,21 +1631,24 @@ def conv_line_ok(dtype, C, axis, dil):
     return dtype in _DT and LIB.query("seg_conv_line_ok", _DT[dtype], C, axis, dil) == 1
 
 
+def conv_line_bias_ok(dtype, C, axis, dil):
+    """conv_line_ok for the classes of conv_line_bias: C = 40 as well."""
+    return dtype in _DT and LIB.query("seg_conv_line_bias_ok", _DT[dtype], C, axis, dil) == 1
+
+
 def conv_line_geom(dtype, N, H, W, C):
-    """Launch geometry of conv_line on [N,H,W,C]: pixels per tile, grid (= statistic rows), tiles
-    per block, pixels per weight-gradient trip, weight-gradient splits."""
-    vals = [LIB.query("seg_conv_line_geom", _DT[dtype], N, H, W, C, k) for k in range(4)]
+    """Launch geometry of conv_line / conv_line_bias on [N,H,W,C]: pixels per tile, grid (=
+    statistic rows), tiles per block, pixels per weight-gradient trip, weight-gradient splits."""
+    vals = [LIB.query("seg_conv_line_bias_geom", _DT[dtype], N, H, W, C, k) for k in range(4)]
     vals.append(LIB.query("seg_conv_line_wgrad_splits", _DT[dtype], N, H, W, C))
     if min(vals) < 1:
         raise ValueError("conv_line_geom: bad dtype / shape: %s %s" % (dtype, (N, H, W, C)))
     return dict(zip(("tile", "grid", "tiles_per_block", "wgrad_trip", "wgrad_splits"), vals))
 
 
-def conv_line(x, wp, axis, dil, pro=None, out=None, add=None, want_stats=False):
-    """x NHWC [N,H,W,C] (a channel slice is fine); wp [C, 3*C] in x.dtype, taps along `axis`
-    (AXIS_H: a (3,1) kernel, AXIS_W: (1,3)).  Returns (y, stat_partial|None); y = conv (+ add)."""
+def _conv_line(entry, ok, x, wp, bias, axis, dil, pro, out, add, want_stats):
     N, H, W, C, ldx = nhwc(x)
-    if not conv_line_ok(x.dtype, C, axis, dil):
+    if not ok(x.dtype, C, axis, dil):
         raise RuntimeError("conv_line: no kernel for %s C=%d axis=%d dil=%d" % (x.dtype, C, axis, dil))
     assert wp.dtype == x.dtype and wp.is_contiguous() and tuple(wp.shape) == (C, 3 * C)
     mode, ps, pt = _pro(pro)
@@ -1659,11 +1662,32 @@ def conv_line(x, wp, axis, dil, pro=None, out=None, add=None, want_stats=False):
         ldadd = nhwc(add)[4]
     partial = None
     if want_stats:
-        rows = LIB.query("seg_conv_line_geom", _DT[x.dtype], N, H, W, C, 1)
+        rows = LIB.query("seg_conv_line_bias_geom", _DT[x.dtype], N, H, W, C, 1)
         partial = torch.empty((rows, 2, C), dtype=torch.float32, device=x.device)
-    LIB.call("seg_conv_line_fwd", _DT[x.dtype], _p(x), ldx, N, H, W, C, _p(wp), axis, dil, mode,
-             _p(ps), _p(pt), _p(out), ldy, _p(add), ldadd, _p(partial), _stream())
+    head = (_DT[x.dtype], _p(x), ldx, N, H, W, C, _p(wp))
+    tail = (axis, dil, mode, _p(ps), _p(pt), _p(out), ldy, _p(add), ldadd, _p(partial), _stream())
+    if entry == "seg_conv_line_fwd":
+        LIB.call(entry, *head, *tail)
+    else:
+        assert bias is None or (bias.dtype == torch.float32 and bias.numel() == C
+                                and bias.is_contiguous())
+        LIB.call(entry, *head, _p(bias), *tail)
     return out, partial
+
+
+def conv_line(x, wp, axis, dil, pro=None, out=None, add=None, want_stats=False):
+    """x NHWC [N,H,W,C] (a channel slice is fine), C in {16, 32, 64}; wp [C, 3*C] in x.dtype,
+    taps along `axis` (AXIS_H: a (3,1) kernel, AXIS_W: (1,3)).  Returns (y, stat_partial|None);
+    y = conv (+ add)."""
+    return _conv_line("seg_conv_line_fwd", conv_line_ok, x, wp, None, axis, dil, pro, out, add,
+                      want_stats)
+
+
+def conv_line_bias(x, wp, bias, axis, dil, pro=None, out=None, add=None, want_stats=False):
+    """conv_line for C in {16, 32, 40, 64} with a float32 bias [C] (None: no bias), added before
+    `add`, the rounding and the statistics: y = conv + bias (+ add)."""
+    return _conv_line("seg_conv_line_bias_fwd", conv_line_bias_ok, x, wp, bias, axis, dil, pro,
+                      out, add, want_stats)
 
 
 def conv_line_wgrad(x, dy, axis, dil, pro=None):
@@ -1716,3 +1740,54 @@ def ssnbt_tail_bwd(gout, out, gm=None):
     LIB.call("seg_ssnbt_tail_bwd", _DT[out.dtype], _p(gout), nhwc(gout)[4], _p(out), ldo, _p(gm),
              nhwc(gm)[4], N * H * W, C, _stream())
     return gm
+
+
+# ---- EDANet: channel placement for the down-sampler's concat (csrc/edanet.hip) ------------------
+def chan_copy(src, dst, C=None):
+    """dst[..., c] = src[..., c] for c < C (default: src's width), 0 for C <= c < dst's width.
+    src, dst: NHWC views over the same pixels, any channel offset (element-wise)."""
+    N, H, W, Cs, lds = nhwc(src)
+    Nd, Hd, Wd, Cz, ldd = nhwc(dst)
+    C = Cs if C is None else C
+    assert (Nd, Hd, Wd) == (N, H, W) and dst.dtype == src.dtype and 1 <= C <= min(Cs, Cz)
+    LIB.call("seg_chan_copy", _DT[src.dtype], _p(src), lds, _p(dst), ldd, N * H * W, C, Cz,
+             _stream())
+    return dst
+
+
+# ---- EDANet: a pair of line convolutions in one launch (csrc/conv_line_pair.hip) ----------------
+def conv_line_pair_ok(dtype, C, L, dil):
+    """Does the pair kernel serve lines of L pixels (along the SECOND axis) of C channels?"""
+    return dtype in _DT and LIB.query("seg_conv_line_pair_ok", _DT[dtype], C, L, dil) == 1
+
+
+def conv_line_pair(x, wa, bias_a, wb, bias_b, order, dil, pro=None, out=None, add=None,
+                   want_mid=True, want_stats=False, want_mid_sums=False):
+    """mid = lineA(act(x)) + bias_a, y = lineB(mid) + bias_b (+ add) in one launch; order 0: A = H,
+    B = W; 1: A = W, B = H.  wa / wb [C, 3*C] in x.dtype, biases float32 [C] or None.
+    Returns (y, mid|None, stat_partial|None, mid_sums|None)."""
+    N, H, W, C, ldx = nhwc(x)
+    L = W if order == 0 else H
+    if not conv_line_pair_ok(x.dtype, C, L, dil):
+        raise RuntimeError("conv_line_pair: no kernel for %s C=%d line=%d dil=%d"
+                           % (x.dtype, C, L, dil))
+    for w in (wa, wb):
+        assert w.dtype == x.dtype and w.is_contiguous() and tuple(w.shape) == (C, 3 * C)
+    for b in (bias_a, bias_b):
+        assert b is None or (b.dtype == torch.float32 and b.numel() == C and b.is_contiguous())
+    mode, ps, pt = _pro(pro)
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == (N, H, W, C) and out.dtype == x.dtype
+    ldadd = 0
+    if add is not None:
+        assert tuple(add.shape) == (N, H, W, C) and add.dtype == x.dtype
+        ldadd = nhwc(add)[4]
+    mid = torch.empty((N, H, W, C), dtype=x.dtype, device=x.device) if want_mid else None
+    rows = LIB.query("seg_conv_line_pair_rows", N, H, W, order)
+    stat = torch.empty((rows, 2, C), dtype=torch.float32, device=x.device) if want_stats else None
+    msum = torch.empty((rows, C), dtype=torch.float32, device=x.device) if want_mid_sums else None
+    LIB.call("seg_conv_line_pair_fwd", _DT[x.dtype], _p(x), ldx, N, H, W, C, _p(wa), _p(bias_a),
+             _p(wb), _p(bias_b), order, dil, mode, _p(ps), _p(pt), _p(mid), C, _p(out),
+             nhwc(out)[4], _p(add), ldadd, _p(stat), _p(msum), _stream())
+    return out, mid, stat, msum
