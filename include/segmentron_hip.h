@@ -447,6 +447,72 @@ int seg_bn_add_prelu_bwd(int dtype, const void* g, long ldg, const void* a, long
                          const float* tb, const float* alpha, void* g_z, long ldgz, int N, long HW,
                          int C, float* partial, int chunks, void* stream);
 
+/* ---- FPENet's FPE block and MEU module (csrc/fpenet.hip; segmentron/models/fpenet.py:150-247) ----
+ * NHWC, fp32 and bf16.  The channel vector is 4 elements (16 B of fp32, 8 B of bf16): n, every pitch
+ * and every channel offset are multiples of 4, not of 8.  No atomics, fp32 partial rows per (chunk,
+ * image) summed in index order, bit-identical results on every launch, and no image reaches another
+ * image's outputs or rows.  act(x; s, t) = relu(s[c]*x + t[c]).
+ *   seg_fpe_stage_fwd    y = depthwise 3x3 (w the [n,1,3,3] parameter as it is, pad = dilation = dil,
+ *                        stride 1) of in = act(a; sa, ta) + act(b; sb, tb), the sum in fp32 and never
+ *                        rounded; b (with sb, tb, b_act) nullable: stage 0.  n a positive multiple of
+ *                        4 up to 64, dil in 1..8; anything else is an error before any launch.
+ *                        b_act (nullable): act(b) at the centre pixel rounded once, written to a slice
+ *                        of another buffer (pitch ldo).  partial[rows][2][n] (nullable) = sum | sum of
+ *                        squares of the fp32 outputs, rows = seg_fpe_stage_rows(...) (or any
+ *                        chunks * N, chunks in 1..256)
+ *   seg_fpe_act_fwd      y = act(b; sb, tb) over rows of an n-channel slice (the last stage's slice
+ *                        of the concat: seg_bn_apply takes 8-channel vectors in bf16)
+ *   seg_fpe_stage_bwd    with t_k = dy[p - d_k] and dgrad = sum_k t_k * w[k]:
+ *                          ga = mask(a) * dgrad, gb = mask(b) * (dgrad + res)  (mask: s*x + t > 0),
+ *                          pw[rows][9][n] = sum t_k * in[p] (the layout seg_dw_bwd_finalize and
+ *                          seg_dwconv3x3_wgrad_finalize take),
+ *                          pa[rows][2][pa_pitch] at column pa_col = (sum ga | sum ga*a_raw),
+ *                          pb[rows][2][n] = (sum gb | sum gb*b_raw)  (seg_bn_bwd_finalize_p's layout).
+ *                        b, res, gb, pb are null together (stage 0).  dy null (then a, ga, pw, pa are
+ *                        not read): gb = mask(b) * res and pb alone, the last stage's slice.
+ *   seg_fpe_bn_bwd_apply dx = scale*g - c0 - c1*x over rows of an n-channel slice; c0 / c1 null
+ *                        together: dx = scale*g (evaluation-mode BatchNorm).  dx may be g.
+ *   seg_meu_fwd          out = a[n][c]*(sl*L + tl) + sa[p]*(sh*bilinear(Hraw) + th),
+ *                        sa[p] = sigmoid(w_sa[0] * mean_c(sl*L + tl)) also stored as fp32 [N,h,w];
+ *                        L [N,h,w,C], Hraw [N,h2,w2,C], 1 <= h2 <= h, 1 <= w2 <= w, align_corners
+ *                        taps; a fp32 [N][C]; w_sa a device float; C a multiple of 8 up to 128;
+ *                        sl / tl and sh / th nullable in pairs
+ *   seg_meu_bwd_low      dL = a*g + w_sa * sa(1-sa)/C * S[p], S[p] = sum_c g*Hup (the gradient at
+ *                        bn_low's output); p_a[rows][2][C] = (sum_p g*Lbn | in column 0:
+ *                        sum_p sa(1-sa) * mean_c(Lbn) * S), p_bn[rows][2][C] = (sum dL | sum dL*L);
+ *                        rows = seg_meu_rows(N, h, w, C, 0), row = chunk * N + image
+ *   seg_meu_bwd_high     dH[q][c] = sum_p wgt(p,q) * sa[p] * g[p][c] + dpool[n][c]/(h2*w2) (dpool fp32
+ *                        [N][C], nullable), every dH written once; p_bn[rows][2][C] = (sum dH |
+ *                        sum dH*Hraw), rows = seg_meu_rows(N, h2, w2, C, 1) */
+int seg_fpe_stage_rows(int dtype, int N, int H, int W, int n);
+int seg_fpe_stage_fwd(int dtype, const void* a, long lda, const float* sa, const float* ta,
+                      const void* b, long ldb, const float* sb, const float* tb, const float* w,
+                      int dil, void* y, long ldy, void* b_act, long ldo, int N, int H, int W, int n,
+                      float* partial, int rows, void* stream);
+int seg_fpe_act_fwd(int dtype, const void* b, long ldb, const float* sb, const float* tb, void* y,
+                    long ldy, long rows, int n, void* stream);
+int seg_fpe_stage_bwd(int dtype, const void* dy, long lddy, const void* a, long lda, const float* sa,
+                      const float* ta, const void* b, long ldb, const float* sb, const float* tb,
+                      const void* res, long ldres, const float* w, int dil, void* ga, long ldga,
+                      void* gb, long ldgb, int N, int H, int W, int n, float* pw, float* pa,
+                      long pa_pitch, int pa_col, float* pb, int rows, void* stream);
+int seg_fpe_bn_bwd_apply(int dtype, const void* g, long ldg, const void* x, long ldx,
+                         const float* scale, const float* c0, const float* c1, void* dx, long lddx,
+                         long rows, int n, void* stream);
+int seg_meu_rows(int N, int h, int w, int C, int high);
+int seg_meu_fwd(int dtype, const void* L, long ldl, const float* sl, const float* tl, const void* Hr,
+                long ldh, const float* sh, const float* th, const float* a, const float* wsa,
+                void* out, long ldo, float* sa, int N, int h, int w, int h2, int w2, int C,
+                void* stream);
+int seg_meu_bwd_low(int dtype, const void* g, long ldg, const void* L, long ldl, const float* sl,
+                    const float* tl, const void* Hr, long ldh, const float* sh, const float* th,
+                    const float* a, const float* wsa, const float* sa, void* dL, long lddl, int N,
+                    int h, int w, int h2, int w2, int C, float* p_a, float* p_bn, int rows,
+                    void* stream);
+int seg_meu_bwd_high(int dtype, const void* g, long ldg, const float* sa, const void* Hr, long ldh,
+                     const float* dpool, void* dH, long lddh, int N, int h, int w, int h2, int w2,
+                     int C, float* p_bn, int rows, void* stream);
+
 /* ---- F.interpolate(mode='bilinear') ---------------------------------------------------------
  * Replaces segmentron/models/deeplabv3_plus.py:39,44,71; segmentron/modules/module.py:64,96;
  * segmentron/models/segbase.py:83.  NHWC -> NHWC with optional prologue and per-(n,c) multiplier. */

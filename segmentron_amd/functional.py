@@ -2779,3 +2779,258 @@ def concat_alias(buf, parts):
 def image_to_nhwc(x, dtype):
     """NCHW float image -> channel-padded NHWC in the compute dtype (no gradient)."""
     return K.nchw_to_nhwc_pad(x, dtype)
+
+
+# ---- FPENet: the FPE pyramid and the MEU fusion (csrc/fpenet.hip) ---------------------------------
+def _bn_is_few_sample(bn, rows):
+    """The condition under which bn_input_backward takes the one-launch float64 backward."""
+    return (bn.group is None and not isinstance(bn.count, torch.Tensor) and bn.mean is not None
+            and bn.count <= K.SMALL_BN_ROWS and rows <= K.SMALL_BN_ROWS)
+
+
+def _affine_bn_backward(g, x, bn, pb, pw=None, slice_kernel=False):
+    """g: the gradient at the OUTPUT of BatchNorm `bn` over the raw tensor x (any ReLU mask is
+    already in it), pb [R, 2, C]: its rows (sum g | sum g*x) from the kernel that produced g ->
+    (dx written over g, dgamma, dbeta, dW).  pw [Rw, 9, n]: weight-gradient rows of a depthwise
+    3x3, reduced to dW [n,1,3,3] by the same finalize where that launch takes them.  The
+    few-sample path is bn_input_backward's (seg_bn_bwd_small, float64), SyncBatchNorm goes through
+    _bn_bwd_finish.  slice_kernel: x is an n-channel slice whose width / offset need not be whole
+    16-byte vectors of bf16 (seg_fpe_bn_bwd_apply instead of seg_bn_bwd_apply)."""
+    C = x.shape[-1]
+    dW = None
+    if pw is not None:
+        pw = pw.view(pw.shape[0], 9 * pw.shape[-1])
+    if _bn_is_few_sample(bn, x.shape[0] * x.shape[1] * x.shape[2]):
+        dx, dgamma, dbeta = K.bn_bwd_small(g, x, (PRO_AFFINE, bn.scale, bn.shift), bn.count, bn.mean,
+                                           bn.invstd, bn.gamma, None, None, bn.training, out=g)
+        if pw is not None:
+            dW = K.dw_wgrad_finalize(pw, pw.shape[1] // 9)
+        return dx, dgamma, dbeta, dW
+    joint = pw is not None and (bn.group is None or (parallel.mailbox(bn.group) is not None
+                                                     and isinstance(bn.count, torch.Tensor)))
+    if pw is not None and not joint:
+        dW = K.dw_wgrad_finalize(pw, pw.shape[1] // 9)
+    dgamma, dbeta, c0, c1, dWj = _bn_bwd_finish(pb.view(pb.shape[0], 2 * C), bn,
+                                                pw if joint else None)
+    if joint:
+        dW = dWj
+    if not bn.training:
+        c0 = c1 = None
+    if slice_kernel:
+        dx = K.fpe_bn_bwd_apply(g, x, bn.scale, c0, c1, out=g)
+    else:
+        dx = K.bn_bwd_apply(g, x, (PRO_AFFINE, bn.scale, bn.shift), c0, c1, out=g)
+    return dx, dgamma, dbeta, dW
+
+
+_FPE_STAGE0 = os.environ.get("SEG_FPE_STAGE0")  # "0" / "1": force the composed / the new kernel
+
+
+def fpe_stage0_routed(dtype, n, rows):
+    """Does the FORWARD of the pyramid's stage 0 — one operand, bn1's prologue, no side output —
+    run on seg_fpe_stage_fwd rather than on seg_dwconv3x3 with that prologue?  Measured in-graph at
+    the five workload shapes of a 4 x 768 x 768 batch in bf16 (profiles/fpenet.md,
+    tools/fpenet_bench.py), new kernel against depthwise launch: [4,192,192] x 8 10.7 against
+    11.9 us and [4,96,96] x 16 6.4 against 6.9 us, but [4,192,192] x 16 13.6 against 12.3 us and
+    [4,96,96] x 32 8.9 against 6.9 us, each beyond the 0.2 - 0.6 us spread; [4,384,384] x 4 is
+    outside the depthwise kernels' bf16 contract.  Only the two classes that lost take the
+    depthwise launch.  Stages 1 - 3 (two operands) won everywhere by 1.4 - 4.7 x, forward and
+    backward, and every stage-0 backward by 1.1 - 1.5 x: they are not routed.  float32 was not
+    measured and stays on the new kernel."""
+    if _FPE_STAGE0 in ("0", "1"):
+        return _FPE_STAGE0 == "1"
+    if dtype == torch.bfloat16 and (n >= 32 or (n >= 16 and rows >= 4 * 192 * 192)):
+        return False
+    return True
+
+
+class FPEPyrSpec:
+    def __init__(self, act, dils, bns, states, out):
+        self.bn1, self.dils, self.bns, self.states, self.out = act.bn, tuple(dils), bns, states, out
+
+
+class _FPEPyrFn(torch.autograd.Function):
+    """The middle of an FPEBlock (fpenet.py:180-187): four depthwise 3x3 of dilation d_s over the
+    quarters of relu(bn1(u)), stage s reading xs[s] + relu(bn2[s-1](y_{s-1})), each followed by its
+    own BatchNorm + ReLU, concatenated.  One node owns the four stages and the four BatchNorms:
+    the raw stage outputs live in one 4n-channel buffer, the activated concat is written by the
+    NEXT stage's side output (slice 3 by one element-wise pass), so no sum, slice or cat is ever
+    materialised.  Backward runs from stage 3 down: the BatchNorm backward of bn2[s], then one
+    pass (seg_fpe_stage_bwd) that yields stage s's slice of bn1's gradient, the masked gradient of
+    y_{s-1} (with conv3's data gradient `res` for that slice joined), the weight-gradient rows and
+    both BatchNorms' rows."""
+
+    @staticmethod
+    def forward(ctx, u, g1, b1, w0, w1, w2, w3, g20, b20, g21, b21, g22, b22, g23, b23, spec):
+        N, H, W, C4 = u.shape
+        n = C4 // 4
+        bn1 = spec.bn1
+        ws = [w.detach().contiguous() for w in (w0, w1, w2, w3)]
+        yraw = torch.empty((N, H, W, C4), dtype=u.dtype, device=u.device)
+        out = spec.out if spec.out is not None else torch.empty_like(yraw)
+        states = []
+        for s in range(4):
+            lo, hi = s * n, (s + 1) * n
+            kw = {}
+            if s:
+                p = states[s - 1]
+                kw = dict(b=yraw[..., lo - n:lo], sb=p.scale, tb=p.shift, b_act=out[..., lo - n:lo])
+            pre = spec.states[s]
+            if s == 0 and n % K.vec_of(u.dtype) == 0 \
+                    and not fpe_stage0_routed(u.dtype, n, N * H * W):
+                y, partial = K.dwconv(u[..., :n], _dw_taps(w0, 1, spec.dils[0]), 1, spec.dils[0],
+                                      (PRO_AFFINE | PRO_RELU, bn1.scale[:n], bn1.shift[:n]),
+                                      yraw[..., :n], pre is None)
+            else:
+                y, partial = K.fpe_stage_fwd(u[..., lo:hi], bn1.scale[lo:hi], bn1.shift[lo:hi],
+                                             ws[s], spec.dils[s], out=yraw[..., lo:hi],
+                                             want_stats=pre is None, **kw)
+            states.append(pre if pre is not None
+                          else finish_bn(spec.bns[s], partial, N * H * W, y=y))
+        K.fpe_act_fwd(yraw[..., 3 * n:], states[3].scale, states[3].shift, out=out[..., 3 * n:])
+        spec.states, spec.bns, spec.out = states, None, None
+        ctx.spec = spec
+        ctx.save_for_backward(u, yraw, *ws)
+        return out
+
+    @staticmethod
+    def backward(ctx, res):
+        u, yraw, *ws = ctx.saved_tensors
+        spec = ctx.spec
+        bn1, st, dils = spec.bn1, spec.states, spec.dils
+        N, H, W, C4 = u.shape
+        n = C4 // 4
+        if res.dtype != u.dtype or not _sum_n_operand_ok(res, 4) or res.storage_offset() % 4:
+            res = res.to(u.dtype).contiguous()
+        rows = K.fpe_stage_rows(u.dtype, N, H, W, n)
+        gA = torch.empty((N, H, W, C4), dtype=u.dtype, device=u.device)
+        pa = torch.empty((rows, 2, C4), dtype=torch.float32, device=u.device)
+        dWs, dgs, dbs = [None] * 4, [None] * 4, [None] * 4
+        # the last stage's slice: its only consumer is conv3
+        _, gb, _, _, pb = K.fpe_stage_bwd(None, None, None, None, None, dils[3],
+                                          b=yraw[..., 3 * n:], sb=st[3].scale, tb=st[3].shift,
+                                          res=res[..., 3 * n:])
+        pw = None
+        for s in (3, 2, 1, 0):
+            lo, hi = s * n, (s + 1) * n
+            # (pw: the rows of stage s + 1's weight gradient ride in this BatchNorm's finalize)
+            dy, dgs[s], dbs[s], dW = _affine_bn_backward(gb, yraw[..., lo:hi], st[s], pb, pw,
+                                                         slice_kernel=True)
+            if s < 3:
+                dWs[s + 1] = dW
+            kw = {}
+            if s:
+                kw = dict(b=yraw[..., lo - n:lo], sb=st[s - 1].scale, tb=st[s - 1].shift,
+                          res=res[..., lo - n:lo])
+            _, gb, pw, _, pb = K.fpe_stage_bwd(dy, u[..., lo:hi], bn1.scale[lo:hi],
+                                               bn1.shift[lo:hi], ws[s], dils[s], ga=gA[..., lo:hi],
+                                               pa=pa, pa_col=lo, **kw)
+        dWs[0] = K.dw_wgrad_finalize(pw.view(rows, 9 * n), n)
+        du, dg1, db1, _ = _affine_bn_backward(gA, u, bn1, pa)
+        return (du, dg1, db1, *dWs, dgs[0], dbs[0], dgs[1], dbs[1], dgs[2], dbs[2], dgs[3], dbs[3],
+                None)
+
+
+def fpe_pyramid(act_u, convs, bns, out=None):
+    """act_u: Act of conv1's raw output [N,H,W,4n] with bn1 pending (its ReLU is implied); convs /
+    bns: the FPEBlock's four depthwise 3x3 nn.Conv2d (n channels each, padding = dilation in 1..8)
+    and their BatchNorms.  -> the plain activated concat [N,H,W,4n] (written into `out`)."""
+    u = act_u.t
+    N, H, W, C4 = u.shape
+    if act_u.bn is None or len(convs) != 4 or len(bns) != 4 or C4 % 16 != 0:
+        raise NotImplementedError("fpe_pyramid: four stages over a 4n-channel tensor (n a multiple "
+                                  "of 4) whose BatchNorm is pending")
+    n = C4 // 4
+    for c in convs:
+        if not (c.kernel_size == (3, 3) and c.groups == n and c.in_channels == n
+                and c.padding[0] == c.dilation[0] and c.stride[0] == 1 and c.bias is None):
+            raise NotImplementedError("fpe_pyramid: depthwise 3x3, stride 1, padding = dilation")
+        K.fpe_stage_check(n, int(c.dilation[0]))
+    for b in bns:
+        if is_group_norm(b):
+            raise NotImplementedError("fpe_pyramid: the stages hand statistics to a BatchNorm")
+    # evaluation-mode states are made here: finish_bn keeps the running statistics for backward
+    # only while gradients are enabled, and they are not inside an autograd node's forward
+    states = [None if uses_batch_stats(b) else finish_bn(b, None, N * H * W) for b in bns]
+    spec = FPEPyrSpec(act_u, [int(c.dilation[0]) for c in convs], list(bns), states, out)
+    g1, b1 = act_u.params
+    args = [u, g1, b1] + [c.weight for c in convs]
+    for b in bns:
+        args += [b.weight, b.bias]
+    return _FPEPyrFn.apply(*args, spec)
+
+
+class MEUSpec:
+    def __init__(self, low, high, out):
+        self.bn_l, self.bn_h, self.out = low.bn, high.bn, out
+
+
+def _aff(bn):
+    return None if bn is None else (bn.scale, bn.shift)
+
+
+class _MEUFn(torch.autograd.Function):
+    """The tail of the MEUModule (fpenet.py:232-245):
+        out = ca[n,c] * bn_low(L) + sa[n,h,w] * bilinear(bn_high(Hraw)),
+        sa = sigmoid(w_sa * mean_c bn_low(L)),  ca = sigmoid(relu(ca_conv(mean_hw bn_high(Hraw))))
+    in one pass over the full-resolution map.  The pooled [N, C] arithmetic (ca_conv, relu,
+    sigmoid and their backward) is torch on the device in float32; the per-image sums come from
+    seg_apply_pool_fwd.  It lives inside this node because the gather at high-level resolution
+    takes the pool's gradient with it: backward is one pass at low-level resolution (dL, da,
+    d w_sa, bn_low's rows), the [N, C] chain, and one gather (dH with the pool's share, bn_high's
+    rows)."""
+
+    @staticmethod
+    def forward(ctx, L, gl, bl, Hr, gh, bh, w_ca, w_sa, spec):
+        N, h2, w2, C = Hr.shape
+        aff_l, aff_h = _aff(spec.bn_l), _aff(spec.bn_h)
+        pro = (PRO_NONE, None, None) if aff_h is None else (PRO_AFFINE, aff_h[0], aff_h[1])
+        _, sums = K.apply_pool(Hr, pro, want_y=False)
+        pooled = sums / float(h2 * w2)
+        Wc = w_ca.detach().float().reshape(C, C)
+        z = pooled @ Wc.t()
+        a = torch.sigmoid(torch.relu(z)).contiguous()
+        wsa = w_sa.detach().float().reshape(1).contiguous()
+        out, sa = K.meu_fwd(L, aff_l, Hr, aff_h, a, wsa, out=spec.out)
+        spec.out = None
+        ctx.spec = spec
+        ctx.save_for_backward(L, Hr, a, z, pooled, Wc, wsa, sa)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        L, Hr, a, z, pooled, Wc, wsa, sa = ctx.saved_tensors
+        s = ctx.spec
+        C = L.shape[-1]
+        aff_l, aff_h = _aff(s.bn_l), _aff(s.bn_h)
+        if g.dtype != L.dtype or not _sum_n_operand_ok(g, 4) or g.storage_offset() % 4:
+            g = g.to(L.dtype).contiguous()
+        dL, da, dwsa, pbl = K.meu_bwd_low(g, L, aff_l, Hr, aff_h, a, wsa, sa)
+        dz = da * a * (1.0 - a) * (z > 0).float()
+        dWc = (dz.t() @ pooled).reshape(C, C, 1, 1)
+        dpool = (dz @ Wc).contiguous()
+        dH, pbh = K.meu_bwd_high(g, sa, Hr, dpool)
+        dgl = dbl = dgh = dbh = None
+        if s.bn_l is not None:
+            dL, dgl, dbl, _ = _affine_bn_backward(dL, L, s.bn_l, pbl)
+        if s.bn_h is not None:
+            dH, dgh, dbh, _ = _affine_bn_backward(dH, Hr, s.bn_h, pbh)
+        return dL, dgl, dbl, dH, dgh, dbh, dWc, dwsa.reshape(1, 1, 1, 1), None
+
+
+def meu_fuse(act_low, act_high, ca_conv, sa_conv, out=None):
+    """act_low [N,h,w,C] / act_high [N,h2,w2,C]: the raw outputs of conv1x1_low / conv1x1_high
+    with their BatchNorms pending (no ReLU); ca_conv: nn.Conv2d(C, C, 1, bias=False); sa_conv:
+    nn.Conv2d(1, 1, 1, bias=False).  -> the plain fused map [N,h,w,C]."""
+    if act_low.relu or act_high.relu:
+        raise ValueError("meu_fuse: an operand carries a pending ReLU")
+    C = int(act_low.t.shape[-1])
+    K.meu_check(C, tuple(act_low.t.shape[1:3]), tuple(act_high.t.shape[1:3]))
+    if tuple(ca_conv.weight.shape) != (C, C, 1, 1) or ca_conv.bias is not None \
+            or sa_conv.weight.numel() != 1 or sa_conv.bias is not None:
+        raise NotImplementedError("meu_fuse: ca_conv is a bias-free 1x1 C -> C convolution and "
+                                  "sa_conv a bias-free 1 -> 1 one")
+    gl, bl = act_low.params
+    gh, bh = act_high.params
+    return _MEUFn.apply(act_low.t, gl, bl, act_high.t, gh, bh, ca_conv.weight, sa_conv.weight,
+                        MEUSpec(act_low, act_high, out))

@@ -1791,3 +1791,247 @@ def conv_line_pair(x, wa, bias_a, wb, bias_b, order, dil, pro=None, out=None, ad
              _p(wb), _p(bias_b), order, dil, mode, _p(ps), _p(pt), _p(mid), C, _p(out),
              nhwc(out)[4], _p(add), ldadd, _p(stat), _p(msum), _stream())
     return out, mid, stat, msum
+
+
+# ---- FPENet's FPE pyramid stages and MEU fusion (csrc/fpenet.hip) ---------------------------------
+FPE_MAX_N, FPE_MAX_DIL, MEU_MAX_C = 64, 8, 128
+
+
+def fpe_stage_check(n, dil):
+    """The contract of seg_fpe_stage_fwd / _bwd, on the host and before any tensor is read."""
+    if not (isinstance(n, int) and n >= 4 and n % 4 == 0 and n <= FPE_MAX_N):
+        raise ValueError("fpe_stage: n=%r is not a positive multiple of 4 up to %d"
+                         % (n, FPE_MAX_N))
+    if not (isinstance(dil, int) and 1 <= dil <= FPE_MAX_DIL):
+        raise ValueError("fpe_stage: dilation %r is not in 1..%d" % (dil, FPE_MAX_DIL))
+
+
+def meu_check(C, low_hw, high_hw):
+    """The contract of seg_meu_fwd / _bwd_low / _bwd_high."""
+    if not (C >= 8 and C % 8 == 0 and C <= MEU_MAX_C):
+        raise ValueError("meu: C=%r is not a positive multiple of 8 up to %d" % (C, MEU_MAX_C))
+    (h, w), (h2, w2) = low_hw, high_hw
+    if not (1 <= h2 <= h and 1 <= w2 <= w):
+        raise ValueError("meu: the high-level map %dx%d is not within the low-level map %dx%d"
+                         % (h2, w2, h, w))
+
+
+def _fpe_slice(t, like, what):
+    if t.dtype != like.dtype or tuple(t.shape) != tuple(like.shape):
+        raise ValueError("%s: expected %s %s, got %s %s"
+                         % (what, tuple(like.shape), like.dtype, tuple(t.shape), t.dtype))
+    ld = nhwc(t)[4]
+    if ld % 4 != 0 or t.storage_offset() % 4 != 0:
+        raise ValueError("%s: pitch %d / offset %d are not multiples of 4"
+                         % (what, ld, t.storage_offset()))
+    return ld
+
+
+def _fpe_vecs(n, what, *vs):
+    for v in vs:
+        if not (v.is_cuda and v.dtype == torch.float32 and v.numel() == n and v.is_contiguous()):
+            raise ValueError("%s: per-channel parameters are contiguous float32 [%d] device tensors"
+                             % (what, n))
+
+
+def fpe_stage_rows(dtype, N, H, W, n):
+    rows = LIB.query("seg_fpe_stage_rows", _DT[dtype], N, H, W, n)
+    if rows < 1:
+        raise ValueError("seg_fpe_stage_rows(%s, %d, %d, %d, %d): out of contract"
+                         % (dtype, N, H, W, n))
+    return rows
+
+
+def fpe_stage_fwd(a, sa, ta, w, dil, b=None, sb=None, tb=None, b_act=None, out=None,
+                  want_stats=True):
+    """-> (y, partial fp32 [rows, 2, n] | None): y = depthwise 3x3 (w [n,1,3,3], pad = dilation =
+    dil) of relu(sa*a + ta) + relu(sb*b + tb) on n-channel NHWC slices (n, pitches and offsets
+    multiples of 4); b None: stage 0.  b_act: an NHWC slice that receives relu(sb*b + tb)."""
+    n = int(a.shape[-1])
+    fpe_stage_check(n, dil)
+    if (b is None) != (sb is None) or (b is None) != (tb is None) or (b is None and b_act is not None):
+        raise ValueError("fpe_stage_fwd: b, sb and tb go together, and b_act needs b")
+    N, H, W, _, lda = nhwc(a)
+    _fpe_slice(a, a, "fpe_stage_fwd a")
+    _fpe_vecs(n, "fpe_stage_fwd", sa, ta, *([] if b is None else [sb, tb]))
+    if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
+            and tuple(w.shape) == (n, 1, 3, 3)):
+        raise ValueError("fpe_stage_fwd: w is a contiguous float32 [%d,1,3,3] device tensor" % n)
+    if out is None:
+        out = torch.empty((N, H, W, n), dtype=a.dtype, device=a.device)
+    ldy = _fpe_slice(out, a, "fpe_stage_fwd out")
+    ldb = _fpe_slice(b, a, "fpe_stage_fwd b") if b is not None else 0
+    ldo = _fpe_slice(b_act, a, "fpe_stage_fwd b_act") if b_act is not None else 0
+    rows = fpe_stage_rows(a.dtype, N, H, W, n)
+    partial = torch.empty((rows, 2, n), dtype=torch.float32, device=a.device) if want_stats \
+        else None
+    LIB.call("seg_fpe_stage_fwd", _DT[a.dtype], _p(a), lda, _p(sa), _p(ta), _p(b), ldb, _p(sb),
+             _p(tb), _p(w), dil, _p(out), ldy, _p(b_act), ldo, N, H, W, n, _p(partial), rows,
+             _stream())
+    return out, partial
+
+
+def fpe_act_fwd(b, sb, tb, out=None):
+    """relu(sb*b + tb) on an n-channel NHWC slice (n a multiple of 4) -> out."""
+    n = int(b.shape[-1])
+    if n < 4 or n % 4 != 0:
+        raise ValueError("fpe_act_fwd: n=%d is not a positive multiple of 4" % n)
+    N, H, W, _, ldb = nhwc(b)
+    _fpe_slice(b, b, "fpe_act_fwd b")
+    _fpe_vecs(n, "fpe_act_fwd", sb, tb)
+    if out is None:
+        out = torch.empty((N, H, W, n), dtype=b.dtype, device=b.device)
+    ldy = _fpe_slice(out, b, "fpe_act_fwd out")
+    LIB.call("seg_fpe_act_fwd", _DT[b.dtype], _p(b), ldb, _p(sb), _p(tb), _p(out), ldy, N * H * W,
+             n, _stream())
+    return out
+
+
+def fpe_bn_bwd_apply(g, x, scale, c0=None, c1=None, out=None):
+    """dx = scale*g - c0 - c1*x on an n-channel NHWC slice (c0 / c1 None: scale*g); out may be g."""
+    n = int(g.shape[-1])
+    if n < 4 or n % 4 != 0:
+        raise ValueError("fpe_bn_bwd_apply: n=%d is not a positive multiple of 4" % n)
+    N, H, W, _, ldg = nhwc(g)
+    _fpe_slice(g, g, "fpe_bn_bwd_apply g")
+    ldx = _fpe_slice(x, g, "fpe_bn_bwd_apply x")
+    if out is None:
+        out = torch.empty((N, H, W, n), dtype=g.dtype, device=g.device)
+    lddx = _fpe_slice(out, g, "fpe_bn_bwd_apply out")
+    LIB.call("seg_fpe_bn_bwd_apply", _DT[g.dtype], _p(g), ldg, _p(x), ldx, _p(scale), _p(c0),
+             _p(c1), _p(out), lddx, N * H * W, n, _stream())
+    return out
+
+
+def fpe_stage_bwd(dy, a, sa, ta, w, dil, b=None, sb=None, tb=None, res=None, ga=None, gb=None,
+                  pa=None, pa_col=0):
+    """One pass over (dy, a, b, res) -> (ga, gb, pw [rows, 9, n], pa, pb [rows, 2, n]).
+    ga = mask(a) * dgrad, gb = mask(b) * (dgrad + res); pa: [rows, 2, P] fp32 whose columns
+    pa_col .. pa_col + n receive (sum ga | sum ga*a_raw) (a fresh [rows, 2, n] if None).
+    dy None (with a, sa, ta, w None): gb = mask(b) * res and pb only — the last stage's slice."""
+    ref = b if dy is None else dy
+    n = int(ref.shape[-1])
+    fpe_stage_check(n, dil)
+    if (b is None) != (res is None) or (b is None) != (sb is None) or (b is None) != (tb is None) \
+            or (b is None and dy is None):
+        raise ValueError("fpe_stage_bwd: b, sb, tb and res go together (and dy or b is given)")
+    N, H, W, _, _ = nhwc(ref)
+    rows = fpe_stage_rows(ref.dtype, N, H, W, n)
+    dev = ref.device
+    lddy = lda = ldga = ldb = ldres = ldgb = 0
+    pw = pb = None
+    pitch = 0
+    if dy is not None:
+        lddy = _fpe_slice(dy, ref, "fpe_stage_bwd dy")
+        lda = _fpe_slice(a, ref, "fpe_stage_bwd a")
+        _fpe_vecs(n, "fpe_stage_bwd", sa, ta)
+        if not (w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
+                and tuple(w.shape) == (n, 1, 3, 3)):
+            raise ValueError("fpe_stage_bwd: w is a contiguous float32 [%d,1,3,3] device tensor" % n)
+        if ga is None:
+            ga = torch.empty((N, H, W, n), dtype=ref.dtype, device=dev)
+        ldga = _fpe_slice(ga, ref, "fpe_stage_bwd ga")
+        pw = torch.empty((rows, 9, n), dtype=torch.float32, device=dev)
+        if pa is None:
+            pa = torch.empty((rows, 2, n), dtype=torch.float32, device=dev)
+        pitch = pa.shape[2]
+        if not (pa.dtype == torch.float32 and pa.is_contiguous() and pa.dim() == 3
+                and tuple(pa.shape[:2]) == (rows, 2) and pa_col % 4 == 0
+                and 0 <= pa_col and pa_col + n <= pitch):
+            raise ValueError("fpe_stage_bwd: partial_a is a contiguous float32 [%d, 2, P] array "
+                             "with %d + %d <= P" % (rows, pa_col, n))
+    else:
+        a = sa = ta = w = ga = pa = None
+    if b is not None:
+        ldb = _fpe_slice(b, ref, "fpe_stage_bwd b")
+        ldres = _fpe_slice(res, ref, "fpe_stage_bwd res")
+        _fpe_vecs(n, "fpe_stage_bwd", sb, tb)
+        if gb is None:
+            gb = torch.empty((N, H, W, n), dtype=ref.dtype, device=dev)
+        ldgb = _fpe_slice(gb, ref, "fpe_stage_bwd gb")
+        pb = torch.empty((rows, 2, n), dtype=torch.float32, device=dev)
+    else:
+        gb = None
+    LIB.call("seg_fpe_stage_bwd", _DT[ref.dtype], _p(dy), lddy, _p(a), lda, _p(sa), _p(ta), _p(b),
+             ldb, _p(sb), _p(tb), _p(res), ldres, _p(w), dil, _p(ga), ldga, _p(gb), ldgb, N, H, W, n,
+             _p(pw), _p(pa), pitch, pa_col, _p(pb), rows, _stream())
+    return ga, gb, pw, pa, pb
+
+
+def _meu_rows(N, h, w, C, high):
+    rows = LIB.query("seg_meu_rows", N, h, w, C, 1 if high else 0)
+    if rows < 1:
+        raise ValueError("seg_meu_rows(%d, %d, %d, %d): out of contract" % (N, h, w, C))
+    return rows
+
+
+def _meu_operands(L, Hr, what):
+    C = int(L.shape[-1])
+    meu_check(C, (int(L.shape[1]), int(L.shape[2])), (int(Hr.shape[1]), int(Hr.shape[2])))
+    N, h, w, _, ldl = nhwc(L)
+    N2, h2, w2, C2, ldh = nhwc(Hr)
+    if N2 != N or C2 != C or Hr.dtype != L.dtype:
+        raise ValueError("%s: the maps disagree: %s %s / %s %s"
+                         % (what, tuple(L.shape), L.dtype, tuple(Hr.shape), Hr.dtype))
+    _fpe_slice(L, L, what + " L")
+    _fpe_slice(Hr, Hr, what + " H")
+    return N, h, w, h2, w2, C, ldl, ldh
+
+
+def _meu_aff(aff):
+    return (None, None) if aff is None else aff
+
+
+def meu_fwd(L, aff_l, Hr, aff_h, a, w_sa, out=None):
+    """-> (out [N,h,w,C], sa fp32 [N,h,w]): out = a[n][c]*(sl*L + tl) + sa*(sh*bilinear(Hr) + th),
+    sa = sigmoid(w_sa * mean_c(sl*L + tl)); aff_* = (scale, shift) | None; a fp32 [N, C]; w_sa a
+    float32 device tensor of one element."""
+    N, h, w, h2, w2, C, ldl, ldh = _meu_operands(L, Hr, "meu_fwd")
+    _nc(a, N, C, "meu_fwd a")
+    if not (w_sa.is_cuda and w_sa.dtype == torch.float32 and w_sa.numel() == 1):
+        raise ValueError("meu_fwd: w_sa is a float32 device tensor of one element")
+    (sl, tl), (sh, th) = _meu_aff(aff_l), _meu_aff(aff_h)
+    if out is None:
+        out = torch.empty((N, h, w, C), dtype=L.dtype, device=L.device)
+    ldo = _fpe_slice(out, L, "meu_fwd out")
+    sa = torch.empty((N, h, w), dtype=torch.float32, device=L.device)
+    LIB.call("seg_meu_fwd", _DT[L.dtype], _p(L), ldl, _p(sl), _p(tl), _p(Hr), ldh, _p(sh), _p(th),
+             _p(a), _p(w_sa), _p(out), ldo, _p(sa), N, h, w, h2, w2, C, _stream())
+    return out, sa
+
+
+def meu_bwd_low(g, L, aff_l, Hr, aff_h, a, w_sa, sa, out=None):
+    """-> (dL at bn_low's output, da fp32 [N, C], d w_sa fp32 [1], p_bn [rows, 2, C] =
+    (sum dL | sum dL*L))."""
+    N, h, w, h2, w2, C, ldl, ldh = _meu_operands(L, Hr, "meu_bwd_low")
+    _nc(a, N, C, "meu_bwd_low a")
+    ldg = _fpe_slice(g, L, "meu_bwd_low g")
+    (sl, tl), (sh, th) = _meu_aff(aff_l), _meu_aff(aff_h)
+    if out is None:
+        out = torch.empty((N, h, w, C), dtype=L.dtype, device=L.device)
+    ldo = _fpe_slice(out, L, "meu_bwd_low out")
+    rows = _meu_rows(N, h, w, C, False)
+    p_a = torch.empty((rows, 2, C), dtype=torch.float32, device=L.device)
+    p_bn = torch.empty((rows, 2, C), dtype=torch.float32, device=L.device)
+    LIB.call("seg_meu_bwd_low", _DT[L.dtype], _p(g), ldg, _p(L), ldl, _p(sl), _p(tl), _p(Hr), ldh,
+             _p(sh), _p(th), _p(a), _p(w_sa), _p(sa), _p(out), ldo, N, h, w, h2, w2, C, _p(p_a),
+             _p(p_bn), rows, _stream())
+    chunks = rows // N
+    s = p_a.view(chunks, N * 2 * C)
+    s = (s[0] if chunks == 1 else colsum(s, f64=False)).view(N, 2, C)
+    return out, s[:, 0, :].contiguous(), s[:, 1, 0].sum().view(1), p_bn
+
+
+def meu_bwd_high(g, sa, Hr, dpool=None, out=None):
+    """-> (dH at bn_high's output [N,h2,w2,C], p_bn [rows, 2, C] = (sum dH | sum dH*Hr)):
+    dH[q] = sum_p wgt(p, q) * sa[p] * g[p] + dpool[n] / (h2*w2)."""
+    N, h, w, h2, w2, C, ldg, ldh = _meu_operands(g, Hr, "meu_bwd_high")
+    _nc(dpool, N, C, "meu_bwd_high dpool")
+    if out is None:
+        out = torch.empty((N, h2, w2, C), dtype=g.dtype, device=g.device)
+    ldo = _fpe_slice(out, Hr, "meu_bwd_high out")
+    rows = _meu_rows(N, h2, w2, C, True)
+    p_bn = torch.empty((rows, 2, C), dtype=torch.float32, device=g.device)
+    LIB.call("seg_meu_bwd_high", _DT[g.dtype], _p(g), ldg, _p(sa), _p(Hr), ldh, _p(dpool), _p(out),
+             ldo, N, h, w, h2, w2, C, _p(p_bn), rows, _stream())
+    return out, p_bn

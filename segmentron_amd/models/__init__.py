@@ -14,3 +14,4 @@ from .cgnet import CGNet  # noqa: F401
 from .lednet import LEDNet  # noqa: F401
 from .espnetv2 import ESPNetV2  # noqa: F401
 from .edanet import EDANet  # noqa: F401
+from .fpenet import FPENet  # noqa: F401
