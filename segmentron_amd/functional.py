@@ -226,13 +226,43 @@ def flush_bn_counters():
         del _PENDING_COUNTERS[:]
 
 
+# The BatchNorm-backward launch policy: every autograd node asks these four and restates none.
+def _bn_sums_exchanged_in_kernel(bn):
+    """SyncBatchNorm whose finalize kernel exchanges the backward sums itself (peer mailbox over its
+    group, global count on the device); else column sums -> all-reduce -> finalize."""
+    return (bn.group is not None and parallel.mailbox(bn.group) is not None
+            and isinstance(bn.count, torch.Tensor))
+
+
+def _bn_finalize_takes_wgrad_rows(bn):
+    """Can the finalize launch reduce a depthwise 3x3's weight-gradient rows too
+    (_bn_bwd_finish(pw=))?  Single-process BatchNorm, or SyncBatchNorm on the mailbox."""
+    return bn.group is None or _bn_sums_exchanged_in_kernel(bn)
+
+
+def _bn_is_few_sample(bn, rows):
+    """Few samples per channel (rows = N*H*W): dx is the remainder of cancelling terms — one
+    float64 launch (seg_bn_bwd_small) instead of reduce + finalize + fp32 apply."""
+    return (bn.group is None and not isinstance(bn.count, torch.Tensor) and bn.mean is not None
+            and bn.count <= K.SMALL_BN_ROWS and rows <= K.SMALL_BN_ROWS)
+
+
+def _bn_backward_is_plain(bn):
+    """Training-mode, single-process BatchNorm off the few-sample path: its backward is reduce ->
+    finalize -> bn_bwd_apply, the chain a parked gradient can join.  (Not the negation of
+    _bn_is_few_sample: evaluation mode and SyncBatchNorm are neither, and this is asked in
+    forward, by the BatchNorm's own count alone.)"""
+    return (bn.training and bn.group is None and not isinstance(bn.count, torch.Tensor)
+            and bn.count > K.SMALL_BN_ROWS)
+
+
 def _sync_bwd_finalize(partial, bn):
     """SyncBatchNorm backward sums [R, 2C] -> (dgamma, dbeta, c0, c1): inside the finalize kernel
     when the peer mailbox is active, else column sums -> all-reduce -> finalize."""
-    box = parallel.mailbox(bn.group)
     scale = parallel.grad_scale(bn.group)
-    if box is not None and isinstance(bn.count, torch.Tensor):
-        return K.bn_bwd_finalize_p_sync(box, partial, bn.count, bn.mean, bn.invstd, bn.gamma, scale)
+    if _bn_sums_exchanged_in_kernel(bn):
+        return K.bn_bwd_finalize_p_sync(parallel.mailbox(bn.group), partial, bn.count, bn.mean,
+                                        bn.invstd, bn.gamma, scale)
     sums = parallel.allreduce_backward_sums(K.colsum(partial), bn.group)
     return K.bn_bwd_finalize(sums, bn.count, bn.mean, bn.invstd, bn.gamma, scale)
 
@@ -241,8 +271,7 @@ def _bn_bwd_finish(pb, bn, pw=None):
     """BatchNorm-backward partials pb [R, 2C] -> (dgamma, dbeta, c0, c1, dW).  pw: the raw
     weight-gradient partials [Rw, 9C] of a fused depthwise backward, reduced to dW [C,1,3,3] on the
     way — by the same launch (K.dw_bwd_finalize*) where that kernel takes the rows; dW is None
-    without them.  (With pw, a SyncBatchNorm has its peer mailbox: _DwFn.backward asks for pw
-    only then.)"""
+    without them.  (Callers pass pw only where _bn_finalize_takes_wgrad_rows.)"""
     dW = None
     if pw is not None and pb.shape[0] <= 1024:
         if bn.group is None:
@@ -268,11 +297,7 @@ def bn_input_backward(g, x, bn, relu, chan_mul=None, inplace=False, elem_mul=Non
                             out=g if inplace else None, elem_mul=elem_mul)
         return dx, None, None
     pro = (mode, bn.scale, bn.shift)
-    if (bn.group is None and not isinstance(bn.count, torch.Tensor) and bn.mean is not None
-            and bn.count <= K.SMALL_BN_ROWS and g.dim() == 4
-            and g.shape[0] * g.shape[1] * g.shape[2] <= K.SMALL_BN_ROWS):
-        # few samples per channel: dx is the remainder of cancelling terms — one float64 launch
-        # (seg_bn_bwd_small) instead of reduce + finalize + fp32 apply
+    if g.dim() == 4 and _bn_is_few_sample(bn, g.shape[0] * g.shape[1] * g.shape[2]):
         return K.bn_bwd_small(g, x, pro, bn.count, bn.mean, bn.invstd, bn.gamma, chan_mul,
                               elem_mul, bn.training, out=g if inplace else None)
     partial = K.bn_bwd_reduce_partial(g, x, pro, chan_mul, elem_mul)
@@ -282,6 +307,38 @@ def bn_input_backward(g, x, bn, relu, chan_mul=None, inplace=False, elem_mul=Non
     dx = K.bn_bwd_apply(g, x, pro, c0, c1, chan_mul, out=g if inplace else None,
                         elem_mul=elem_mul)
     return dx, dgamma, dbeta
+
+
+def _affine_bn_backward(g, x, bn, pb, pw=None, slice_kernel=False):
+    """g: the gradient at the OUTPUT of BatchNorm `bn` over the raw tensor x (any ReLU mask is
+    already in it), pb [R, 2, C]: its rows (sum g | sum g*x) from the kernel that produced g ->
+    (dx written over g, dgamma, dbeta, dW).  pw [Rw, 9, n]: weight-gradient rows of a depthwise
+    3x3, reduced to dW [n,1,3,3] by the same finalize where that launch takes them.  The
+    few-sample path is bn_input_backward's (seg_bn_bwd_small, float64), SyncBatchNorm goes through
+    _bn_bwd_finish.  slice_kernel: x is an n-channel slice whose width / offset need not be whole
+    16-byte vectors of bf16 (seg_fpe_bn_bwd_apply instead of seg_bn_bwd_apply)."""
+    C = x.shape[-1]
+    dW = None
+    if pw is not None:
+        pw = pw.view(pw.shape[0], 9 * pw.shape[-1])
+    if _bn_is_few_sample(bn, x.shape[0] * x.shape[1] * x.shape[2]):
+        dx, dgamma, dbeta = K.bn_bwd_small(g, x, (PRO_AFFINE, bn.scale, bn.shift), bn.count, bn.mean,
+                                           bn.invstd, bn.gamma, None, None, bn.training, out=g)
+        if pw is not None:
+            dW = K.dw_wgrad_finalize(pw, pw.shape[1] // 9)
+        return dx, dgamma, dbeta, dW
+    if pw is not None and not _bn_finalize_takes_wgrad_rows(bn):
+        dW, pw = K.dw_wgrad_finalize(pw, pw.shape[1] // 9), None
+    dgamma, dbeta, c0, c1, dWj = _bn_bwd_finish(pb.view(pb.shape[0], 2 * C), bn, pw)
+    if pw is not None:
+        dW = dWj
+    if not bn.training:
+        c0 = c1 = None
+    if slice_kernel:
+        dx = K.fpe_bn_bwd_apply(g, x, bn.scale, c0, c1, out=g)
+    else:
+        dx = K.bn_bwd_apply(g, x, (PRO_AFFINE, bn.scale, bn.shift), c0, c1, out=g)
+    return dx, dgamma, dbeta, dW
 
 
 # ----------------------------------------------------------------------------- weight packing
@@ -547,9 +604,60 @@ def _dw_taps(weight, stride, dil, reversed=False):
 def _dw_bwd_is_fused(stride, dil, C, wdtype):
     """Is this depthwise layer's backward the one-pass kind (masked data gradient, weight-gradient
     partials and BatchNorm sums from one launch)?  Every stride-1 layer, and stride 2 / dilation 1
-    on its own kernel (csrc/dwconv_s2.hip).  _DwFn.backward runs by it and low_feat_fork arms a
-    fork on it: one statement, so that the two cannot drift."""
+    on its own kernel (csrc/dwconv_s2.hip).  dw_backward chooses its half by it — every autograd
+    node's depthwise backward goes through there — and low_feat_fork arms a fork on it."""
     return stride == 1 or (stride == 2 and dil == 1 and C % 4 == 0 and wdtype == torch.float32)
+
+
+# The depthwise 3x3 backward, the Python counterpart of dw_route (csrc/dwconv.hip: each launch's
+# kernel family): which launches make it up, which form of the taps they read and the layout their
+# weight gradient comes back in are decided below and nowhere else.  Callers hand in the [C,1,3,3]
+# parameter and get its gradient in that shape.
+def dw_backward_raw_ok(stride, dil, C, wdtype):
+    """May a caller ask dw_backward for raw_dw?  Where the one-pass kernel writes the
+    weight-gradient rows in the parameter's own layout, which the finalize launches read."""
+    return _dw_bwd_is_fused(stride, dil, C, wdtype) and (stride == 2 or K.dw_tiled(stride, dil))
+
+
+def dw_backward_fused(x, dy, weight, stride, dil, pro=None, want_bn=False, raw_dw=False, res=None,
+                      res_sum=False, out=None):
+    """The one-pass half -> (g masked by the prologue's ReLU, + res, written to `out`; dW fp32
+    [C,1,3,3], or with raw_dw its unreduced rows [R, 9C] for _bn_bwd_finish(pw=); the
+    BatchNorm-backward rows [R, 2C] with want_bn)."""
+    if stride == 2:
+        assert res is None
+        return K.dwconv_bwd_fused_s2(x, dy, weight.detach().contiguous(), pro, want_bn=want_bn,
+                                     raw_dw=raw_dw, out=out)
+    tiled = K.dw_tiled(1, dil)  # these kernels produce dW in torch's layout, too
+    assert tiled or not raw_dw
+    g, dW, pb = K.dwconv_bwd_fused(x, dy, _dw_taps(weight, 1, dil), dil, pro, want_bn=want_bn,
+                                   torch_layout=tiled, raw_dw=raw_dw, res=res, out=out,
+                                   res_sum=res_sum)
+    return g, (dW if tiled else K.dw_torch_layout(dW)), pb
+
+
+def dw_backward_split(x, dy, weight, stride, dil, pro=None, want_dx=True):
+    """The two-launch half -> (g, dW [C,1,3,3]).  g (None without want_dx; stride 1: the forward
+    kernel on reversed taps) is NOT masked yet: bn_input_backward or the caller's own pass does."""
+    tiled = K.dw_tiled(stride, dil)
+    dW = K.dwconv_wgrad(x, dy, stride, dil, pro, torch_layout=tiled)
+    if not tiled:
+        dW = K.dw_torch_layout(dW)
+    g = None
+    if want_dx:
+        w = _dw_taps(weight, stride, dil, reversed=stride == 1)
+        g = K.dwconv_dgrad(dy, w, stride, dil, (x.shape[1], x.shape[2]))
+    return g, dW
+
+
+def dw_backward(x, dy, weight, stride, dil, pro=None, want_dx=True, **fused_args):
+    """-> (g, dW, pb, fused): dw_backward_fused(**fused_args) where _dw_bwd_is_fused and a data
+    gradient is wanted, else dw_backward_split (pb None).  raw_dw (dw_backward_raw_ok) and res
+    (stride 1) are asked only where the fused half runs."""
+    if want_dx and _dw_bwd_is_fused(stride, dil, weight.shape[0], weight.dtype):
+        return (*dw_backward_fused(x, dy, weight, stride, dil, pro, **fused_args), True)
+    assert not fused_args.get("raw_dw") and fused_args.get("res") is None
+    return (*dw_backward_split(x, dy, weight, stride, dil, pro, want_dx), None, False)
 
 
 def _round_up(v, m):
@@ -742,10 +850,9 @@ class _FoldConvFn(torch.autograd.Function):
         if not s.drop_const:  # eval-mode consumer: the constant term carries gradient
             db = K.bn_bwd_reduce(dy, dy, (PRO_NONE, None, None))[:O].float()
         dW, dsdt = K.fold_bwd_reduce(weight.detach().view(O, C), dwp, bn.scale, bn.shift, db)
-        box = parallel.mailbox(bn.group) if bn.group is not None else None
-        if box is not None and isinstance(bn.count, torch.Tensor):
+        if _bn_sums_exchanged_in_kernel(bn):
             dgamma, dbeta, c0, c1 = K.fold_bwd_finalize_sync(
-                box, dsdt, bn.count, bn.mean, bn.invstd, bn.gamma, bn.scale,
+                parallel.mailbox(bn.group), dsdt, bn.count, bn.mean, bn.invstd, bn.gamma, bn.scale,
                 parallel.grad_scale(bn.group))
         else:
             if bn.group is not None:
@@ -798,60 +905,42 @@ class _DwFn(torch.autograd.Function):
         f = s.fork
         if f is not None:
             f.closed = True  # (a consumer that runs after this one keeps its gradient)
-        tiled = K.dw_tiled(s.stride, s.dil)  # these kernels produce dW in torch's layout, too
-        # One pass over (dy, x): masked data gradient + weight-gradient partials + BN sums
-        # (_dw_bwd_is_fused).  Otherwise: weight gradient and data gradient separately.
-        fused = _dw_bwd_is_fused(s.stride, s.dil, C, weight.dtype)
-        fused_s2 = fused and s.stride == 2
-        if ctx.needs_input_grad[0] and fused:
-            # raw: leave the weight-gradient partials to the launch that reduces the
-            # BatchNorm-backward ones (single-process BatchNorm, or SyncBatchNorm on the mailbox)
-            raw = bn is not None and (fused_s2 or tiled) and \
-                (bn.group is None or (parallel.mailbox(bn.group) is not None
-                                      and isinstance(bn.count, torch.Tensor)))
-            if fused_s2:
-                g, dW, pb = K.dwconv_bwd_fused_s2(x, dy, weight.detach().contiguous(), s.pro,
-                                                  want_bn=bn is not None, raw_dw=raw)
-            else:
-                res, as_sum = None, False
-                if f is not None and f.g is not None and f.kind in (GradFork.POST, GradFork.SUM):
-                    as_sum = f.kind == GradFork.SUM
-                    if bn is None and (K.dwconv_bwd_fused_sum_ok(x.dtype, C, s.dil) if as_sum
-                                       else K.dwconv_bwd_fused_add_ok(s.dil)):
-                        res = s.fork.take()  # the other consumer's gradient rides in the store
-                        if res.dtype != x.dtype or tuple(res.shape) != tuple(x.shape):
-                            s.fork.g, res = res, None
-                g, dW, pb = K.dwconv_bwd_fused(x, dy, _dw_taps(weight, 1, s.dil), s.dil, s.pro,
-                                               want_bn=bn is not None, torch_layout=tiled,
-                                               raw_dw=raw, res=res, res_sum=as_sum)
-                if not tiled:
-                    dW = K.dw_torch_layout(dW)
-            if bn is None:
-                dx = g  # plain / ReLU input: the masked gradient is final
-            else:
-                dgamma, dbeta, c0, c1, dWsum = _bn_bwd_finish(pb, bn, dW if raw else None)
-                if raw:
-                    dW = dWsum
-                if not bn.training:
-                    c0 = c1 = None
-                add = add_pro = None
-                if f is not None and f.g is not None and f.kind in (GradFork.RAW, GradFork.PRE) \
-                        and f.g.dtype == g.dtype and tuple(f.g.shape) == tuple(g.shape):
-                    # the other consumer's gradient: w.r.t. the raw tensor, or (PRE) w.r.t. the
-                    # activated one with the coefficients of its own BatchNorm backward
-                    add_pro = f.coef if f.kind == GradFork.PRE else None
-                    add = f.take()
-                # the ReLU mask is already in g: apply only the affine part of the BN backward
-                dx = K.bn_bwd_apply(g, x, (PRO_AFFINE, bn.scale, bn.shift), c0, c1, out=g, add=add,
-                                    add_pro=add_pro)
-        else:
-            dW = K.dwconv_wgrad(x, dy, s.stride, s.dil, s.pro, torch_layout=tiled)
-            if not tiled:
-                dW = K.dw_torch_layout(dW)
-            if ctx.needs_input_grad[0]:  # (stride 1: the forward kernel on reversed taps)
-                w = _dw_taps(weight, s.stride, s.dil, reversed=s.stride == 1)
-                g = K.dwconv_dgrad(dy, w, s.stride, s.dil, (x.shape[1], x.shape[2]))
+        want_dx = ctx.needs_input_grad[0]
+        # raw: the launch that reduces the BatchNorm-backward rows takes the weight gradient's too
+        raw = want_dx and bn is not None and _bn_finalize_takes_wgrad_rows(bn) \
+            and dw_backward_raw_ok(s.stride, s.dil, C, weight.dtype)
+        res, as_sum = None, False
+        if want_dx and s.stride == 1 and f is not None and f.g is not None \
+                and f.kind in (GradFork.POST, GradFork.SUM):
+            as_sum = f.kind == GradFork.SUM
+            if bn is None and (K.dwconv_bwd_fused_sum_ok(x.dtype, C, s.dil) if as_sum
+                               else K.dwconv_bwd_fused_add_ok(s.dil)):
+                res = s.fork.take()  # the other consumer's gradient rides in the store
+                if res.dtype != x.dtype or tuple(res.shape) != tuple(x.shape):
+                    s.fork.g, res = res, None
+        g, dW, pb, fused = dw_backward(x, dy, weight, s.stride, s.dil, s.pro, want_dx,
+                                       want_bn=bn is not None, raw_dw=raw, res=res, res_sum=as_sum)
+        if not fused:
+            if want_dx:
                 dx, dgamma, dbeta = bn_input_backward(g, x, bn, s.relu, inplace=True)
+        elif bn is None:
+            dx = g  # plain / ReLU input: the masked gradient is final
+        else:
+            dgamma, dbeta, c0, c1, dWsum = _bn_bwd_finish(pb, bn, dW if raw else None)
+            if raw:
+                dW = dWsum
+            if not bn.training:
+                c0 = c1 = None
+            add = add_pro = None
+            if f is not None and f.g is not None and f.kind in (GradFork.RAW, GradFork.PRE) \
+                    and f.g.dtype == g.dtype and tuple(f.g.shape) == tuple(g.shape):
+                # the other consumer's gradient: w.r.t. the raw tensor, or (PRE) w.r.t. the
+                # activated one with the coefficients of its own BatchNorm backward
+                add_pro = f.coef if f.kind == GradFork.PRE else None
+                add = f.take()
+            # the ReLU mask is already in g: apply only the affine part of the BN backward
+            dx = K.bn_bwd_apply(g, x, (PRO_AFFINE, bn.scale, bn.shift), c0, c1, out=g, add=add,
+                                add_pro=add_pro)
         if f is not None and f.g is not None and dx is not None:
             if f.kind == GradFork.PRE:  # (armed only where the fused backward runs: *_fork below)
                 raise RuntimeError("a gradient parked for the depthwise backward's BatchNorm pass "
@@ -1303,10 +1392,8 @@ class _ApplyPoolFn(torch.autograd.Function):
         g_y, g_p = grads if s.want_y else (None, grads[0])
         N, H, W, C = x.shape
         if g_y is not None:
-            if g_y.dtype != x.dtype or not _sum_n_operand_ok(g_y, K.vec_of(x.dtype)):
-                g_y, own = g_y.to(x.dtype).contiguous(), True
-            else:
-                own = s.own_grad
+            g_in, g_y = g_y, _grad_operand(g_y, x.dtype, K.vec_of(x.dtype))
+            own = s.own_grad or g_y is not g_in  # (a copy made here is nobody else's)
         if g_p is None:
             if g_y is None:
                 return None, None, None, None
@@ -1339,8 +1426,7 @@ class _ChanGateFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, a2 = ctx.saved_tensors
         N, H, W, C = x.shape
-        if dy.dtype != x.dtype or not _sum_n_operand_ok(dy, K.vec_of(x.dtype)):
-            dy = dy.to(x.dtype).contiguous()
+        dy = _grad_operand(dy, x.dtype, K.vec_of(x.dtype))
         need = ctx.needs_input_grad
         dx, da, dradd = K.chan_gate_bwd(dy, x, a2, ctx.identity, want_dx=need[0], want_da=need[1],
                                         want_dradd=need[3])
@@ -1478,7 +1564,7 @@ class _ForkFn(torch.autograd.Function):
             for g in gs[2:]:
                 acc = acc + g
             return acc, None
-        gs = [g if _sum_n_operand_ok(g, vec) else g.contiguous() for g in gs]
+        gs = [_grad_operand(g, g.dtype, vec) for g in gs]
         return K.sum_n(gs), None
 
 
@@ -1489,6 +1575,18 @@ def _sum_n_operand_ok(g, vec):
         return K.nhwc(g)[4] % vec == 0
     except RuntimeError:
         return False
+
+
+def _grad_operand(g, dtype, vec, align=1, min_pitch=0):
+    """An incoming gradient as a kernel operand: of `dtype`, _sum_n_operand_ok at `vec`, starting
+    on a multiple of `align` elements, rows of at least `min_pitch` channels (zero-padded).
+    Autograd hands over whatever the consumer produced; anything else is copied once."""
+    if g.dtype != dtype or not _sum_n_operand_ok(g, vec) or g.storage_offset() % align \
+            or K.nhwc(g)[4] < min_pitch:
+        g = g.to(dtype).contiguous()
+        if g.shape[-1] < min_pitch:
+            g = torch.nn.functional.pad(g, (0, min_pitch - g.shape[-1]))
+    return g
 
 
 def fork(t, n):
@@ -1646,12 +1744,9 @@ class _GroupNormFn(torch.autograd.Function):
     def backward(ctx, dz):
         y, weight, mean_rstd = ctx.saved_tensors
         N, H, W, C = y.shape
-        if dz.dtype != y.dtype:
-            dz = dz.to(y.dtype)
         # (a channel slice of a concat gradient is fine as long as its pitch and start keep the
         # 16-byte vectors whole; anything else — a broadcast, an odd pitch — is copied once)
-        if not _sum_n_operand_ok(dz, K.vec_of(y.dtype)):
-            dz = dz.contiguous()
+        dz = _grad_operand(dz, y.dtype, K.vec_of(y.dtype))
         coef, contrib = K.gn_bwd_finalize(K.gn_moments(dz, y), H * W, ctx.groups, mean_rstd, weight)
         dx = K.gn_affine(dz, y, coef) if ctx.needs_input_grad[0] else None
         dw = db = None
@@ -1765,13 +1860,6 @@ def dwconv_plain(act, conv, out=None):
     spec = ConvSpec(act, conv.stride[0], conv.padding[0], conv.dilation[0], out, want_stats=False)
     g, b = act.params
     return _DwFn.apply(act.t, g, b, conv.weight, spec)
-
-
-def _bn_backward_is_plain(bn):
-    """Training-mode, single-process BatchNorm off the few-sample path: its backward is reduce ->
-    finalize -> bn_bwd_apply, the chain a parked gradient can join."""
-    return (bn.training and bn.group is None and not isinstance(bn.count, torch.Tensor)
-            and bn.count > K.SMALL_BN_ROWS)
 
 
 def conv_skip_fork(act, conv, dw):
@@ -1977,11 +2065,8 @@ class _BNPReLUFn(torch.autograd.Function):
         C = al.numel()
         if g_y is None and g_p is None:
             return None, None, None, None, None
-        if g_y is not None and (g_y.dtype != x.dtype or not _sum_n_operand_ok(g_y, K.vec_of(x.dtype))
-                                or K.nhwc(g_y)[4] < K.round_up8(C)):
-            g_y = g_y.to(x.dtype).contiguous()
-            if g_y.shape[-1] != K.round_up8(C):
-                g_y = torch.nn.functional.pad(g_y, (0, K.round_up8(C) - g_y.shape[-1]))
+        if g_y is not None:
+            g_y = _grad_operand(g_y, x.dtype, K.vec_of(x.dtype), min_pitch=K.round_up8(C))
         v = None if g_p is None else g_p.reshape(N, C).float().contiguous()
         g_z, dalpha = K.prelu_bwd(g_y, v, x, al, None if bn is None else bn.scale,
                                   None if bn is None else bn.shift)
@@ -2087,19 +2172,12 @@ class _CGJointFn(torch.autograd.Function):
     def backward(ctx, g):
         x, w_loc, w_sur = ctx.saved_tensors
         C, d = x.shape[-1], ctx.dil
-        if g.dtype != x.dtype or not _sum_n_operand_ok(g, K.vec_of(x.dtype)):
-            g = g.to(x.dtype).contiguous()
-        tiled = K.dw_tiled(1, d)
-        g_sur, dws, _ = K.dwconv_bwd_fused(x, g[..., C:], _dw_taps(w_sur, 1, d), d, None,
-                                           torch_layout=tiled)
-        if not tiled:
-            dws = K.dw_torch_layout(dws)
+        g = _grad_operand(g, x.dtype, K.vec_of(x.dtype))
+        g_sur, dws, _ = dw_backward_fused(x, g[..., C:], w_sur, 1, d)
         if K.dwconv_bwd_fused_add_ok(1) and C % 4 == 0:
-            dx, dwl, _ = K.dwconv_bwd_fused(x, g[..., :C], _dw_taps(w_loc, 1, 1), 1, None,
-                                            torch_layout=True, res=g_sur)
+            dx, dwl, _ = dw_backward_fused(x, g[..., :C], w_loc, 1, 1, res=g_sur)
         else:
-            g_loc, dwl, _ = K.dwconv_bwd_fused(x, g[..., :C], _dw_taps(w_loc, 1, 1), 1, None,
-                                               torch_layout=True)
+            g_loc, dwl, _ = dw_backward_fused(x, g[..., :C], w_loc, 1, 1)
             dx = K.sum_n([g_loc, g_sur])
         return dx, dwl, dws, None
 
@@ -2146,26 +2224,6 @@ class EESPPyrSpec:
         self.partial = None
 
 
-def _dw_branch_bwd(x, dy, weight, stride, dil):
-    """Backward of one plain-input depthwise 3x3 branch -> (dx contribution, dW [n,1,3,3]): the
-    kernels _DwFn.backward runs for a layer without a pending BatchNorm."""
-    C = weight.shape[0]
-    tiled = K.dw_tiled(stride, dil)
-    if _dw_bwd_is_fused(stride, dil, C, weight.dtype):
-        if stride == 2:
-            g, dW, _ = K.dwconv_bwd_fused_s2(x, dy, weight.detach().contiguous(), None)
-            return g, dW
-        g, dW, _ = K.dwconv_bwd_fused(x, dy, _dw_taps(weight, 1, dil), dil, None,
-                                      torch_layout=tiled)
-    else:
-        dW = K.dwconv_wgrad(x, dy, stride, dil, None, torch_layout=tiled)
-        w = _dw_taps(weight, stride, dil, reversed=stride == 1)
-        g = K.dwconv_dgrad(dy, w, stride, dil, (x.shape[1], x.shape[2]))
-    if not tiled:
-        dW = K.dw_torch_layout(dW)
-    return g, dW
-
-
 class _EESPPyrFn(torch.autograd.Function):
     """cat_j(sum_{i <= j} spp_dw[i](x)) of the EESP unit (module.py:194-199) with the statistics of
     br_after_cat's BatchNorm.  Forward: the joint kernel where eesp_pyramid_routed, else the four
@@ -2202,12 +2260,11 @@ class _EESPPyrFn(torch.autograd.Function):
         x, *ws = ctx.saved_tensors
         spec = ctx.spec
         n = x.shape[-1]
-        if g.dtype != x.dtype or not _sum_n_operand_ok(g, K.vec_of(x.dtype)):
-            g = g.to(x.dtype).contiguous()
-        S = K.eesp_suffix_sum(g)
+        S = K.eesp_suffix_sum(_grad_operand(g, x.dtype, K.vec_of(x.dtype)))
         gs, dWs = [], []
         for j, (w, d) in enumerate(zip(ws, spec.dils)):
-            gj, dW = _dw_branch_bwd(x, S[..., j * n:(j + 1) * n], w, spec.stride, d)
+            # (plain input: either half's data gradient is final)
+            gj, dW, _, _ = dw_backward(x, S[..., j * n:(j + 1) * n], w, spec.stride, d)
             gs.append(gj)
             dWs.append(dW)
         dx = K.sum_n(gs) if ctx.needs_input_grad[0] else None
@@ -2244,8 +2301,7 @@ class _AvgPool3x3s2Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if not _sum_n_operand_ok(g, K.vec_of(g.dtype)):
-            g = g.contiguous()
+        g = _grad_operand(g, g.dtype, K.vec_of(g.dtype))
         return K.avgpool3x3s2_bwd(g, ctx.in_hw), None
 
 
@@ -2295,8 +2351,7 @@ class _BNAddPReLUFn(torch.autograd.Function):
         a, b, al = ctx.saved_tensors
         s = ctx.spec
         C = a.shape[-1]
-        if g.dtype != a.dtype or not _sum_n_operand_ok(g, K.vec_of(a.dtype)):
-            g = g.to(a.dtype).contiguous()
+        g = _grad_operand(g, a.dtype, K.vec_of(a.dtype))
         g_z, dalpha = K.bn_add_prelu_bwd(g, a, b, al, _affine_of(s.bn_a, s.lead, C, a.device),
                                          _affine_of(s.bn_b, 0, C, a.device))
         da = db = dga = dba = dgb = dbb = None
@@ -2445,8 +2500,7 @@ class _LineConvFn(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         s = ctx.spec
         C, dt = x.shape[-1], x.dtype
-        if dy.dtype != dt or not _sum_n_operand_ok(dy, K.vec_of(dt)):
-            dy = dy.to(dt).contiguous()
+        dy = _grad_operand(dy, dt, K.vec_of(dt))
         dW = K.conv_line_wgrad(x, dy, s.axis, s.dil, s.pro).view(weight.shape)
         dbias = None
         if ctx.has_bias and s.drop_bias:
@@ -2568,8 +2622,7 @@ class _LinePairFn(torch.autograd.Function):
         s = ctx.spec
         N, H, W, C = x.shape
         dt = x.dtype
-        if dy.dtype != dt or not _sum_n_operand_ok(dy, K.vec_of(dt)):
-            dy = dy.to(dt).contiguous()
+        dy = _grad_operand(dy, dt, K.vec_of(dt))
         axis_a, axis_b = (K.AXIS_H, K.AXIS_W) if s.order == 0 else (K.AXIS_W, K.AXIS_H)
         dWb = K.conv_line_wgrad(mid, dy, axis_b, s.dil).view(wb.shape)
         dbb = None
@@ -2650,9 +2703,7 @@ class _SSnbtTailFn(torch.autograd.Function):
     def backward(ctx, gout):
         y0, y1, out = ctx.saved_tensors
         s = ctx.spec
-        if gout.dtype != out.dtype or not _sum_n_operand_ok(gout, K.vec_of(out.dtype)):
-            gout = gout.to(out.dtype).contiguous()
-        gm = K.ssnbt_tail_bwd(gout, out)
+        gm = K.ssnbt_tail_bwd(_grad_operand(gout, out.dtype, K.vec_of(out.dtype)), out)
         h = out.shape[-1] // 2
         d0, dg0, db0 = bn_input_backward(gm[..., :h], y0, s.bn0, True)
         d1, dg1, db1 = bn_input_backward(gm[..., h:], y1, s.bn1, True)
@@ -2782,47 +2833,6 @@ def image_to_nhwc(x, dtype):
 
 
 # ---- FPENet: the FPE pyramid and the MEU fusion (csrc/fpenet.hip) ---------------------------------
-def _bn_is_few_sample(bn, rows):
-    """The condition under which bn_input_backward takes the one-launch float64 backward."""
-    return (bn.group is None and not isinstance(bn.count, torch.Tensor) and bn.mean is not None
-            and bn.count <= K.SMALL_BN_ROWS and rows <= K.SMALL_BN_ROWS)
-
-
-def _affine_bn_backward(g, x, bn, pb, pw=None, slice_kernel=False):
-    """g: the gradient at the OUTPUT of BatchNorm `bn` over the raw tensor x (any ReLU mask is
-    already in it), pb [R, 2, C]: its rows (sum g | sum g*x) from the kernel that produced g ->
-    (dx written over g, dgamma, dbeta, dW).  pw [Rw, 9, n]: weight-gradient rows of a depthwise
-    3x3, reduced to dW [n,1,3,3] by the same finalize where that launch takes them.  The
-    few-sample path is bn_input_backward's (seg_bn_bwd_small, float64), SyncBatchNorm goes through
-    _bn_bwd_finish.  slice_kernel: x is an n-channel slice whose width / offset need not be whole
-    16-byte vectors of bf16 (seg_fpe_bn_bwd_apply instead of seg_bn_bwd_apply)."""
-    C = x.shape[-1]
-    dW = None
-    if pw is not None:
-        pw = pw.view(pw.shape[0], 9 * pw.shape[-1])
-    if _bn_is_few_sample(bn, x.shape[0] * x.shape[1] * x.shape[2]):
-        dx, dgamma, dbeta = K.bn_bwd_small(g, x, (PRO_AFFINE, bn.scale, bn.shift), bn.count, bn.mean,
-                                           bn.invstd, bn.gamma, None, None, bn.training, out=g)
-        if pw is not None:
-            dW = K.dw_wgrad_finalize(pw, pw.shape[1] // 9)
-        return dx, dgamma, dbeta, dW
-    joint = pw is not None and (bn.group is None or (parallel.mailbox(bn.group) is not None
-                                                     and isinstance(bn.count, torch.Tensor)))
-    if pw is not None and not joint:
-        dW = K.dw_wgrad_finalize(pw, pw.shape[1] // 9)
-    dgamma, dbeta, c0, c1, dWj = _bn_bwd_finish(pb.view(pb.shape[0], 2 * C), bn,
-                                                pw if joint else None)
-    if joint:
-        dW = dWj
-    if not bn.training:
-        c0 = c1 = None
-    if slice_kernel:
-        dx = K.fpe_bn_bwd_apply(g, x, bn.scale, c0, c1, out=g)
-    else:
-        dx = K.bn_bwd_apply(g, x, (PRO_AFFINE, bn.scale, bn.shift), c0, c1, out=g)
-    return dx, dgamma, dbeta, dW
-
-
 _FPE_STAGE0 = os.environ.get("SEG_FPE_STAGE0")  # "0" / "1": force the composed / the new kernel
 
 
@@ -2900,8 +2910,7 @@ class _FPEPyrFn(torch.autograd.Function):
         bn1, st, dils = spec.bn1, spec.states, spec.dils
         N, H, W, C4 = u.shape
         n = C4 // 4
-        if res.dtype != u.dtype or not _sum_n_operand_ok(res, 4) or res.storage_offset() % 4:
-            res = res.to(u.dtype).contiguous()
+        res = _grad_operand(res, u.dtype, 4, align=4)
         rows = K.fpe_stage_rows(u.dtype, N, H, W, n)
         gA = torch.empty((N, H, W, C4), dtype=u.dtype, device=u.device)
         pa = torch.empty((rows, 2, C4), dtype=torch.float32, device=u.device)
@@ -3003,8 +3012,7 @@ class _MEUFn(torch.autograd.Function):
         s = ctx.spec
         C = L.shape[-1]
         aff_l, aff_h = _aff(s.bn_l), _aff(s.bn_h)
-        if g.dtype != L.dtype or not _sum_n_operand_ok(g, 4) or g.storage_offset() % 4:
-            g = g.to(L.dtype).contiguous()
+        g = _grad_operand(g, L.dtype, 4, align=4)
         dL, da, dwsa, pbl = K.meu_bwd_low(g, L, aff_l, Hr, aff_h, a, wsa, sa)
         dz = da * a * (1.0 - a) * (z > 0).float()
         dWc = (dz.t() @ pooled).reshape(C, C, 1, 1)

@@ -159,14 +159,9 @@ def depthwise_conv3x3_backward(x: torch.Tensor, dy: torch.Tensor, weight: torch.
     pro = _PRO_RELU if relu_in else None
     if K.nhwc(dy)[4] % K.vec_of(dy.dtype) != 0:
         dy = dy.contiguous()
-    tiled = K.dw_tiled(stride, dilation)
-    if tiled:  # one pass: masked data gradient + weight gradient
-        g, dW, _ = K.dwconv_bwd_fused(x, dy, weight, dilation, pro, want_bn=False,
-                                      torch_layout=True)
-        return g, dW
-    dW = K.dw_torch_layout(K.dwconv_wgrad(x, dy, stride, dilation, pro))
-    w = F._dw_taps(weight, stride, dilation, reversed=stride == 1)
-    g = K.dwconv_dgrad(dy, w, stride, dilation, (x.shape[1], x.shape[2]))
+    if K.dw_tiled(stride, dilation):  # this operator's own rule: one pass here only
+        return F.dw_backward_fused(x, dy, weight, stride, dilation, pro)[:2]
+    g, dW = F.dw_backward_split(x, dy, weight, stride, dilation, pro)
     if relu_in:
         g = K.bn_bwd_apply(g, x, _PRO_RELU, out=g)
     return g, dW

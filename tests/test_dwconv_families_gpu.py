@@ -42,6 +42,9 @@ IDS = ["fp32", "bf16"]
 NAN = float("nan")
 MODES = [0, 1, 2, 3, 5, 7]
 F32, BF16 = torch.float32, torch.bfloat16
+# assert_close `fac` of the two weight gradients (shared with tests/test_dw_backward_gpu.py)
+FUSED_DW_FAC = 20
+WGRAD_FAC = {F32: 20, BF16: 100}
 
 
 def K():
@@ -267,7 +270,7 @@ def _check(N, H, W, C, stride, dil, mode, dtype, sl=False, ties=False, seed=1):
     assert gy == [_grid_y_mirror(dtype, C, N, H, W, stride, dil, k) for k in range(3)]
     sfac = 5 if dtype == F32 else 60
     bfac = 5 if dtype == F32 else 300
-    wfac = 20 if dtype == F32 else 100
+    wfac = WGRAD_FAC[dtype]
 
     def out_slice(h, ww):
         P, off = (C + 2 * vec, vec) if sl else (C, 0)
@@ -331,7 +334,7 @@ def _check(N, H, W, C, stride, dil, mode, dtype, sl=False, ties=False, seed=1):
     assert gf.data_ptr() == out.data_ptr() and pb.shape[0] == gyb
     assert_close(to_cpu_nchw(gf), gref, dtype, "fused g")
     border_is_nan(full, off)
-    assert_close(dWf.cpu(), dwref, F32, "fused dW", fac=20)
+    assert_close(dWf.cpu(), dwref, F32, "fused dW", fac=FUSED_DW_FAC)
     sums = K().colsum(pb).cpu()
     gx = gref * x.double()
     assert_close(sums[:C], gref.sum((0, 2, 3)), F32, "fused sum g",
@@ -341,7 +344,7 @@ def _check(N, H, W, C, stride, dil, mode, dtype, sl=False, ties=False, seed=1):
     if tiled:
         g4, dW4, pb4 = K().dwconv_bwd_fused(xd, dyd, w4, dil, pro, want_bn=True, torch_layout=True)
         assert torch.equal(g4, gf) and torch.equal(pb4, pb)
-        assert_close(dW4.cpu(), dwref, F32, "fused dW torch layout", fac=20)
+        assert_close(dW4.cpu(), dwref, F32, "fused dW torch layout", fac=FUSED_DW_FAC)
 
     # ---- the partial rows each launch owns: buffers two rows longer, NaN-filled
     L, p, dt, st = K().LIB, K()._p, K()._DT[dtype], K()._stream()

@@ -46,8 +46,7 @@ def joint_leg(dtype, iters, repeats):
         gy = torch.randn(N, H, W, 2 * C, device="cuda", generator=g).to(dtype)
         wl = torch.randn(C, 1, 3, 3, device="cuda", generator=g) * 0.3
         ws = torch.randn(C, 1, 3, 3, device="cuda", generator=g) * 0.3
-        tiled = K.dw_tiled(1, d)
-        ws_taps = ws if tiled else F.pack_dw_weight(ws)  # (packed once per step, not per call)
+        ws_taps = F._dw_taps(ws, 1, d)  # (packed once per step, not per call)
         buf = torch.empty(N, H, W, 2 * C, device="cuda", dtype=dtype)
 
         def joint_fwd():
@@ -59,17 +58,13 @@ def joint_leg(dtype, iters, repeats):
             return buf, p1, p2
 
         def bwd_pair_sum():
-            g1, dw1, _ = K.dwconv_bwd_fused(x, gy[..., :C], wl, 1, None, torch_layout=True)
-            g2, dw2, _ = K.dwconv_bwd_fused(x, gy[..., C:], ws_taps, d, None, torch_layout=tiled)
-            if not tiled:
-                dw2 = K.dw_torch_layout(dw2)
+            g1, dw1, _ = F.dw_backward_fused(x, gy[..., :C], wl, 1, 1)
+            g2, dw2, _ = F.dw_backward_fused(x, gy[..., C:], ws, 1, d)
             return K.sum_n([g1, g2]), dw1, dw2
 
         def bwd_pair_res():  # what functional._CGJointFn.backward runs
-            g2, dw2, _ = K.dwconv_bwd_fused(x, gy[..., C:], ws_taps, d, None, torch_layout=tiled)
-            if not tiled:
-                dw2 = K.dw_torch_layout(dw2)
-            g1, dw1, _ = K.dwconv_bwd_fused(x, gy[..., :C], wl, 1, None, torch_layout=True, res=g2)
+            g2, dw2, _ = F.dw_backward_fused(x, gy[..., C:], ws, 1, d)
+            g1, dw1, _ = F.dw_backward_fused(x, gy[..., :C], wl, 1, 1, res=g2)
             return g1, dw1, dw2
 
         # the two paths compute the same thing

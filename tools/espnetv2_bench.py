@@ -89,7 +89,7 @@ def pyramid_leg(iters, repeats):
                 x, gy = ops
                 spec = F.EESPPyrSpec(dils, s, False, True)
                 S = F.K.eesp_suffix_sum(gy)
-                gs = [F._dw_branch_bwd(x, S[..., j * n:(j + 1) * n], c.weight, s, d)[0]
+                gs = [F.dw_backward(x, S[..., j * n:(j + 1) * n], c.weight, s, d)[0]
                       for j, (c, d) in enumerate(zip(convs, dils))]
                 return F.K.sum_n(gs), spec
             variants = {"joint_fwd": _rotating(make, fwd(True)),

@@ -115,12 +115,11 @@ def stage_leg(iters, repeats):
                     return K.dwconv(s_in, taps, 1, d, None, t["y"], True)
 
                 def composed_bwd():
-                    if not has_b and F._dw_bwd_is_fused(1, d, n, w.dtype):
-                        g, _, _ = K.dwconv_bwd_fused(a, t["dy"], taps, d, pro_a, want_bn=True,
-                                                     torch_layout=K.dw_tiled(1, d))
+                    if not has_b:  # (stride 1: the one-pass half, as _DwFn.backward runs it)
+                        g = F.dw_backward(a, t["dy"], wparam, 1, d, pro_a, want_bn=True)[0]
                         return K.bn_bwd_apply(g, a, (K.PRO_AFFINE, t["sa"], t["ta"]), t["c0"],
                                               t["c1"], out=t["ga"])
-                    g, _ = F._dw_branch_bwd(s_in if has_b else a, t["dy"], wparam, 1, d)
+                    g = F.dw_backward(s_in, t["dy"], wparam, 1, d)[0]
                     K.bn_bwd_reduce_partial(g, a, pro_a)
                     K.bn_bwd_apply(g, a, pro_a, t["c0"], t["c1"], out=t["ga"])
                     if has_b:
