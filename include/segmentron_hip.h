@@ -513,6 +513,40 @@ int seg_meu_bwd_high(int dtype, const void* g, long ldg, const float* sa, const 
                      const float* dpool, void* dH, long lddh, int N, int h, int w, int h2, int w2,
                      int C, float* p_bn, int rows, void* stream);
 
+/* ---- UNet's encoder skips and padded upsampling (csrc/unet.hip; segmentron/models/unet.py:81-121) --
+ * NHWC, fp32 and bf16, a channel pitch per operand, C a multiple of the 16-byte vector (4 / 8).
+ * No atomics: bit-identical results on every launch.  act = the seg_maxpool_fwd prologue
+ * (pro_mode / scale / shift; the model uses affine + ReLU).
+ *   seg_skip_pool_fwd     one pass over the raw y [N,H,W,C]: skip = act(y) (a slice of a wider
+ *                         buffer) and pooled [N,H/2,W/2,C] (floor) = the 2x2 / stride-2 max of the
+ *                         stored values, i.e. of act(y) rounded to the activation dtype.  A trailing
+ *                         odd row or column goes to skip only; no index tensor.  H, W >= 2.
+ *   seg_skip_pool_bwd     g' = relu_mask * (g_skip + scatter(g_pool)) written densely, the activation
+ *                         recomputed from y; the winner of a window is the first maximum of the
+ *                         rounded activations in row-major order (ATen's max_pool2d rule).
+ *                         partial[rows][2][C] = (sum g' | sum g'*y) of the unrounded fp32 g', the
+ *                         layout seg_bn_bwd_finalize_p takes; rows = seg_skip_pool_bwd_rows(...) (or
+ *                         any 1..65535).  g_skip and g_pool are nullable (a zero gradient).
+ *   seg_bilinear_pad_fwd  seg_bilinear_fwd with a destination window: the resized Ho x Wo map lands at
+ *                         (top, left) of the Hd x Wd map y (a pitched channel slice), the rest of that
+ *                         slice is set to zero: F.pad(F.interpolate(act(x), (Ho, Wo), 'bilinear'))
+ *   seg_bilinear_pad_bwd  gx [N,Hi,Wi,C] gathered from the window of gy [N,Hd,Wd,C] alone */
+int seg_skip_pool_fwd(int dtype, const void* y, long ldy, int N, int H, int W, int C, int pro_mode,
+                      const float* pro_scale, const float* pro_shift, void* skip, long ldskip,
+                      void* pooled, long ldpool, void* stream);
+int seg_skip_pool_bwd_rows(int dtype, int N, int H, int W, int C);
+int seg_skip_pool_bwd(int dtype, const void* g_skip, long ldgs, const void* g_pool, long ldgp,
+                      const void* y, long ldy, int N, int H, int W, int C, int pro_mode,
+                      const float* pro_scale, const float* pro_shift, void* gx, long ldgx,
+                      float* partial, int rows, void* stream);
+int seg_bilinear_pad_fwd(int dtype, const void* x, long ldx, int N, int Hi, int Wi, int C,
+                         int pro_mode, const float* pro_scale, const float* pro_shift, void* y,
+                         long ldy, int Ho, int Wo, int Hd, int Wd, int top, int left,
+                         int align_corners, void* stream);
+int seg_bilinear_pad_bwd(int dtype, void* gx, long ldgx, int N, int Hi, int Wi, int C, const void* gy,
+                         long ldgy, int Ho, int Wo, int Hd, int Wd, int top, int left,
+                         int align_corners, void* stream);
+
 /* ---- F.interpolate(mode='bilinear') ---------------------------------------------------------
  * Replaces segmentron/models/deeplabv3_plus.py:39,44,71; segmentron/modules/module.py:64,96;
  * segmentron/models/segbase.py:83.  NHWC -> NHWC with optional prologue and per-(n,c) multiplier. */

@@ -3042,3 +3042,119 @@ def meu_fuse(act_low, act_high, ca_conv, sa_conv, out=None):
     gh, bh = act_high.params
     return _MEUFn.apply(act_low.t, gl, bl, act_high.t, gh, bh, ca_conv.weight, sa_conv.weight,
                         MEUSpec(act_low, act_high, out))
+
+
+# ---- UNet: the encoder skip + max-pool node and the padded resize (csrc/unet.hip) ------------------
+_UNET_SKIP_POOL = os.environ.get("SEG_UNET_SKIP_POOL")  # "0" / "1": force the existing / fused route
+# (dtype, C) classes in which the fused node measured SLOWER than materialize + max_pool and their
+# backward in the same run (tools/unet_bench.py, profiles/unet.md): they keep the existing route
+_SKIP_POOL_LOST = frozenset()
+
+
+def skip_pool_routed(dtype, C):
+    """Does functional.skip_pool run the fused node for C-channel levels of `dtype`?"""
+    if _UNET_SKIP_POOL in ("0", "1"):
+        return _UNET_SKIP_POOL == "1"
+    return (dtype, C) not in _SKIP_POOL_LOST
+
+
+class SkipPoolSpec:
+    def __init__(self, a, out):
+        self.bn, self.relu, self.pro, self.out = a.bn, a.relu, a.pro, out
+
+
+class _SkipPoolFn(torch.autograd.Function):
+    """(skip, pooled) = (act(y), nn.MaxPool2d(2)(act(y))) of a deferred activation in ONE pass over
+    the raw y (csrc/unet.hip seg_skip_pool_fwd): the skip lands in its slice of the decoder's
+    concat buffer, no index tensor is kept.  Backward receives both gradients at once:
+    seg_skip_pool_bwd recomputes the activation and the windows' winners from y, writes the masked
+    sum and its BatchNorm-backward rows; what follows is the BatchNorm's own launch policy."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, spec):
+        ctx.set_materialize_grads(False)
+        skip, pooled = K.skip_pool_fwd(y, spec.pro, spec.out)
+        spec.out = None  # (it IS skip: kept, ctx -> spec -> skip -> grad_fn -> ctx would be a cycle)
+        ctx.spec = spec
+        ctx.save_for_backward(y)
+        return skip, pooled
+
+    @staticmethod
+    def backward(ctx, g_skip, g_pool):
+        (y,) = ctx.saved_tensors
+        s = ctx.spec
+        if g_skip is None and g_pool is None:
+            return None, None, None, None
+        vec = K.vec_of(y.dtype)
+        if g_skip is not None:
+            g_skip = _grad_operand(g_skip, y.dtype, vec)
+        if g_pool is not None:
+            g_pool = _grad_operand(g_pool, y.dtype, vec)
+        g, pb = K.skip_pool_bwd(g_skip, g_pool, y, s.pro)
+        bn = s.bn
+        if bn is None:
+            return g, None, None, None
+        if _bn_backward_is_plain(bn):
+            dgamma, dbeta, c0, c1 = K.bn_bwd_finalize_p(pb.view(pb.shape[0], -1), bn.count, bn.mean,
+                                                        bn.invstd, bn.gamma)
+            dx = K.bn_bwd_apply(g, y, (PRO_AFFINE, bn.scale, bn.shift), c0, c1, out=g)
+        else:  # few samples, evaluation mode, SyncBatchNorm: the mask is already in g
+            dx, dgamma, dbeta = bn_input_backward(g, y, bn, relu=False, inplace=True)
+        return dx, dgamma, dbeta, None
+
+
+def skip_pool(act, out):
+    """-> (skip, pooled): skip = act(x) written into `out` (the level's channel slice of the
+    decoder's concat buffer), pooled = nn.MaxPool2d(2)(skip).  One autograd node on the fused
+    kernels where skip_pool_routed, else materialize(out=) + max_pool on the same deferred tensor."""
+    t = act.t
+    if t.dim() != 4 or t.shape[1] < 2 or t.shape[2] < 2:
+        raise ValueError("skip_pool: a %s map has no 2x2 window" % (tuple(t.shape),))
+    if tuple(out.shape) != tuple(t.shape) or out.dtype != t.dtype:
+        raise ValueError("skip_pool: out is %s of %s, the activation %s of %s"
+                         % (tuple(out.shape), out.dtype, tuple(t.shape), t.dtype))
+    if not skip_pool_routed(t.dtype, t.shape[-1]):
+        return materialize(act, out=out, force=True), max_pool(act, 2, 2, 0)
+    g, b = act.params
+    return _SkipPoolFn.apply(t, g, b, SkipPoolSpec(act, out))
+
+
+class PlacedResizeSpec:
+    def __init__(self, a, out_hw, place, align_corners, out):
+        self.bn, self.relu, self.pro = a.bn, a.relu, a.pro
+        self.out_hw, self.place, self.align, self.out = out_hw, place, align_corners, out
+
+
+class _BilinearPadFn(torch.autograd.Function):
+    """F.pad(F.interpolate(mode='bilinear')) of a deferred activation into a channel slice of a
+    larger map (unet.py:109-120): one launch writes the window and the zero border; the backward
+    reads the window alone."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, spec):
+        y = K.bilinear_pad(x, spec.out_hw, spec.out, spec.place, spec.pro, spec.align)
+        spec.out = None  # (it IS y)
+        ctx.spec = spec
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        s = ctx.spec
+        g = _grad_operand(g, x.dtype, K.vec_of(x.dtype))
+        ga = K.bilinear_pad_bwd(g, (x.shape[1], x.shape[2]), s.out_hw, s.place, s.align)
+        dx, dgamma, dbeta = bn_input_backward(ga, x, s.bn, s.relu, inplace=True)
+        return dx, dgamma, dbeta, None
+
+
+def bilinear_placed(act, out_hw, out, place=(0, 0), align_corners=True):
+    """bilinear(act, out_hw) written at place = (top, left) of the larger map `out` (a channel slice
+    of a concat buffer), zeros around it.  Where `out` has exactly out_hw there is no pad: the
+    existing launch (functional.bilinear)."""
+    out_hw = tuple(int(v) for v in out_hw)
+    if tuple(out.shape[1:3]) == out_hw and tuple(place) == (0, 0):
+        return bilinear(act, out_hw, align_corners=align_corners, out=out)
+    g, b = act.params
+    return _BilinearPadFn.apply(act.t, g, b, PlacedResizeSpec(act, out_hw, tuple(place),
+                                                              align_corners, out))

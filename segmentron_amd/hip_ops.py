@@ -2035,3 +2035,77 @@ def meu_bwd_high(g, sa, Hr, dpool=None, out=None):
     LIB.call("seg_meu_bwd_high", _DT[g.dtype], _p(g), ldg, _p(sa), _p(Hr), ldh, _p(dpool), _p(out),
              ldo, N, h, w, h2, w2, C, _p(p_bn), rows, _stream())
     return out, p_bn
+
+
+# ---- UNet: encoder skips written in place, padded upsampling (csrc/unet.hip) ----------------------
+def _same_shape(t, shape, like, what):
+    if tuple(t.shape) != tuple(shape) or t.dtype != like.dtype:
+        raise ValueError("%s: expected %s of %s, got %s of %s"
+                         % (what, tuple(shape), like.dtype, tuple(t.shape), t.dtype))
+    return nhwc(t)[4]
+
+
+def skip_pool_rows(dtype, N, H, W, C):
+    """Partial rows of skip_pool_bwd for an [N,H,W,C] level (host only)."""
+    rows = LIB.query("seg_skip_pool_bwd_rows", _DT[dtype], N, H, W, C)
+    if rows < 1:
+        raise ValueError("skip_pool_rows: bad dtype / shape: %s %s" % (dtype, (N, H, W, C)))
+    return rows
+
+
+def skip_pool_fwd(y, pro=None, out=None):
+    """One pass over the raw y: -> (skip = act(y), written into `out` — a channel slice of a concat
+    buffer — where given, pooled [N, H//2, W//2, C] = the 2x2 max of the stored skip)."""
+    N, H, W, C, ldy = nhwc(y)
+    mode, s, t = _pro(pro)
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=y.dtype, device=y.device)
+    lds = _same_shape(out, (N, H, W, C), y, "skip_pool_fwd out")
+    pooled = torch.empty((N, H // 2, W // 2, C), dtype=y.dtype, device=y.device)
+    LIB.call("seg_skip_pool_fwd", _DT[y.dtype], _p(y), ldy, N, H, W, C, int(mode), _p(s), _p(t),
+             _p(out), lds, _p(pooled), C, _stream())
+    return out, pooled
+
+
+def skip_pool_bwd(g_skip, g_pool, y, pro=None, out=None):
+    """-> (g' = relu_mask * (g_skip + scatter(g_pool)) dense [N,H,W,C], partial fp32 [R, 2, C] =
+    (sum g' | sum g'*y)).  Either gradient may be None; the activation and the windows' winners are
+    recomputed from the raw y."""
+    N, H, W, C, ldy = nhwc(y)
+    mode, s, t = _pro(pro)
+    ldgs = 0 if g_skip is None else _same_shape(g_skip, (N, H, W, C), y, "skip_pool_bwd g_skip")
+    ldgp = 0 if g_pool is None else _same_shape(g_pool, (N, H // 2, W // 2, C), y,
+                                                "skip_pool_bwd g_pool")
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=y.dtype, device=y.device)
+    ldgx = _same_shape(out, (N, H, W, C), y, "skip_pool_bwd out")
+    rows = LIB.query("seg_skip_pool_bwd_rows", _DT[y.dtype], N, H, W, C)
+    partial = torch.empty((max(rows, 1), 2, C), dtype=torch.float32, device=y.device)
+    LIB.call("seg_skip_pool_bwd", _DT[y.dtype], _p(g_skip), ldgs, _p(g_pool), ldgp, _p(y), ldy, N, H,
+             W, C, int(mode), _p(s), _p(t), _p(out), ldgx, _p(partial), rows, _stream())
+    return out, partial
+
+
+def bilinear_pad(x, out_hw, out, place=(0, 0), pro=None, align_corners=True):
+    """F.pad(F.interpolate(act(x), out_hw, 'bilinear')) to out's size: the resized map lands at
+    place = (top, left) of `out` [N, Hd, Wd, C] (a channel slice), the rest of `out` is zero."""
+    N, Hi, Wi, C, ldx = nhwc(x)
+    Ho, Wo = out_hw
+    mode, s, t = _pro(pro)
+    Hd, Wd = out.shape[1:3]
+    ldy = _same_shape(out, (N, Hd, Wd, C), x, "bilinear_pad out")
+    LIB.call("seg_bilinear_pad_fwd", _DT[x.dtype], _p(x), ldx, N, Hi, Wi, C, int(mode), _p(s), _p(t),
+             _p(out), ldy, Ho, Wo, Hd, Wd, int(place[0]), int(place[1]), int(align_corners),
+             _stream())
+    return out
+
+
+def bilinear_pad_bwd(gy, in_hw, out_hw, place=(0, 0), align_corners=True):
+    """gy [N, Hd, Wd, C] -> gx [N, Hi, Wi, C], read from the out_hw window at `place` alone."""
+    N, Hd, Wd, C, ldgy = nhwc(gy)
+    Hi, Wi = in_hw
+    gx = torch.empty((N, Hi, Wi, C), dtype=gy.dtype, device=gy.device)
+    LIB.call("seg_bilinear_pad_bwd", _DT[gy.dtype], _p(gx), C, N, Hi, Wi, C, _p(gy), ldgy,
+             out_hw[0], out_hw[1], Hd, Wd, int(place[0]), int(place[1]), int(align_corners),
+             _stream())
+    return gx

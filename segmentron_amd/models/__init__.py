@@ -15,3 +15,4 @@ from .lednet import LEDNet  # noqa: F401
 from .espnetv2 import ESPNetV2  # noqa: F401
 from .edanet import EDANet  # noqa: F401
 from .fpenet import FPENet  # noqa: F401
+from .unet import UNet  # noqa: F401
