@@ -13,7 +13,7 @@
 //                   -> seg_colsum -> [all-reduce] -> seg_bn_bwd_finalize -> (dgamma, dbeta, c0, c1)
 //                   -> seg_bn_bwd_apply:  dx = scale*g' - c0 - c1*x
 // Wavefront (64-lane) layout: lanes run along 16-byte channel vectors of NHWC rows.
-#include "common.h"
+#include "rows.h"
 #include "p2p.h"
 
 namespace seg {
@@ -808,17 +808,6 @@ __global__ __launch_bounds__(EW_THREADS) void dw_bwd_finalize_kernel(
   }
 }
 
-static int pick_cvb_log2_ew(int CV) {
-  int best = 5;
-  double bu = 0;
-  for (int l = 5; l >= 3; --l) {
-    const int b = 1 << l;
-    const double u = (double)CV / (double)(((CV + b - 1) / b) * b);
-    if (u > bu + 1e-9) { bu = u; best = l; }
-  }
-  return best;
-}
-
 // Launch geometry of the row-tile kernels.  r06: a block covers WHOLE rows whenever a row has more
 // than 32 channel vectors (C > 256 in bf16).  With power-of-two column blocks the 91 vectors of a
 // 728-channel row were split over three blocks (512 + 512 + 432 bytes of every 1456-byte pixel,
@@ -830,7 +819,7 @@ struct EwGeom { int lpr, rpb, threads, gx; };
 static EwGeom ew_geom(int CV) {
   EwGeom g;
   if (CV <= 32 || CV > EW_MAX_THREADS) {
-    const int l = pick_cvb_log2_ew(CV);
+    const int l = rows_pick_cvb_log2(CV, 3);
     g.lpr = 1 << l; g.rpb = EW_THREADS >> l; g.threads = EW_THREADS;
     g.gx = (CV + g.lpr - 1) >> l;
     return g;
@@ -1015,12 +1004,7 @@ extern "C" int seg_bn_apply(int dtype, const void* x, long ldx, int mode_x, cons
   const EwGeom geo = ew_geom(a.CV);
   a.lpr = geo.lpr; a.rpb = geo.rpb;
   const dim3 grid = ew_grid2(geo, M);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((bn_apply_kernel<bf16_t>), grid, dim3(geo.threads), 0,
-                       (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((bn_apply_kernel<float>), grid, dim3(geo.threads), 0,
-                       (hipStream_t)stream, a);
+  SEG_LAUNCH_T(bn_apply_kernel, grid, dim3(geo.threads), 0, stream, a);
   return check_launch("bn_apply");
 }
 
@@ -1041,10 +1025,7 @@ extern "C" int seg_sum_n(int dtype, int n, const void* const* xs, const long* ld
   const EwGeom geo = ew_geom(a.CV);
   a.lpr = geo.lpr; a.rpb = geo.rpb;
   const dim3 grid = ew_grid2(geo, M);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((sum_n_kernel<bf16_t>), grid, dim3(geo.threads), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((sum_n_kernel<float>), grid, dim3(geo.threads), 0, (hipStream_t)stream, a);
+  SEG_LAUNCH_T(sum_n_kernel, grid, dim3(geo.threads), 0, stream, a);
   return check_launch("sum_n");
 }
 
@@ -1108,12 +1089,7 @@ extern "C" int seg_bn_bwd_reduce(int dtype, const void* g, long ldg, const void*
   a.lpr = geo.lpr; a.rpb = geo.rpb;
   const int gx = geo.gx;
   const size_t lds = (size_t)geo.threads * 2 * vec * sizeof(float);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16_t>), dim3(gx, grid_y), dim3(geo.threads), lds,
-                       (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<float>), dim3(gx, grid_y), dim3(geo.threads), lds,
-                       (hipStream_t)stream, a);
+  SEG_LAUNCH_T(bn_bwd_reduce_kernel, dim3(gx, grid_y), dim3(geo.threads), lds, stream, a);
   return check_launch("bn_bwd_reduce");
 }
 
@@ -1197,14 +1173,10 @@ static int bn_bwd_apply_launch(const char* name, int dtype, const void* g, long 
   const EwGeom geo = ew_geom(a.CV);
   a.lpr = geo.lpr; a.rpb = geo.rpb;
   const dim3 grid = ew_grid2(geo, M);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) {
-    if (add) hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, true>), grid, dim3(geo.threads), 0, st, a);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16_t, false>), grid, dim3(geo.threads), 0, st, a);
-  } else {
-    if (add) hipLaunchKernelGGL((bn_bwd_apply_kernel<float, true>), grid, dim3(geo.threads), 0, st, a);
-    else hipLaunchKernelGGL((bn_bwd_apply_kernel<float, false>), grid, dim3(geo.threads), 0, st, a);
-  }
+  if (add)
+    SEG_LAUNCH_T((bn_bwd_apply_kernel, true), grid, dim3(geo.threads), 0, stream, a);
+  else
+    SEG_LAUNCH_T((bn_bwd_apply_kernel, false), grid, dim3(geo.threads), 0, stream, a);
   return check_launch(name);
 }
 }  // namespace seg

@@ -70,8 +70,8 @@ __global__ __launch_bounds__(CGN_THREADS) void bn_prelu_fwd_kernel(const PreluAr
     }
   }
   if (a.partial != nullptr)
-    cgn_block_reduce<VEC, 1>(smem, acc, a.cvb_log2, a.C,
-                             a.partial + ((long)blockIdx.y * a.N + n) * a.C, 0);
+    rows_block_reduce<VEC, 1>(smem, acc, a.cvb_log2, blockIdx.x, a.C,
+                              a.partial + ((long)blockIdx.y * a.N + n) * a.C, 0);
 }
 
 template <typename T>
@@ -122,8 +122,8 @@ __global__ __launch_bounds__(CGN_THREADS) void prelu_bwd_kernel(const PreluArgs 
       stg16(GZ + row * a.ldy + c0, Vec<T>::pack(g));
     }
   }
-  cgn_block_reduce<VEC, 1>(smem, acc, a.cvb_log2, a.C,
-                           a.partial + ((long)blockIdx.y * a.N + n) * a.C, 0);
+  rows_block_reduce<VEC, 1>(smem, acc, a.cvb_log2, blockIdx.x, a.C,
+                            a.partial + ((long)blockIdx.y * a.N + n) * a.C, 0);
 }
 
 // ------------------------------------------------------------------------------- joint depthwise
@@ -194,46 +194,34 @@ __global__ __launch_bounds__(CGN_THREADS) void cg_joint_fwd_kernel(const JointAr
   }
   // partial[row][2][2C]: k = 0..3 -> (sum | loc), (sum | sur), (sq | loc), (sq | sur)
   if (a.partial != nullptr)
-    cgn_block_reduce<V, 4>(smem, acc, a.cvb_log2, a.C,
-                           a.partial + ((long)blockIdx.y * a.N + n) * 4 * a.C, a.C);
+    rows_block_reduce<V, 4>(smem, acc, a.cvb_log2, blockIdx.x, a.C,
+                            a.partial + ((long)blockIdx.y * a.N + n) * 4 * a.C, a.C);
 }
 
 static int prelu_common(const char* what, int dtype, int N, long HW, int C, const long* lds,
                         int nld, int chunks, PreluArgs* a) {
   const int vec = dtype == DT_BF16 ? 8 : 4;
-  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "%s: bad dtype %d", what, dtype);
-  SEG_REQUIRE(N >= 1 && N <= 65535 && HW >= 1 && C >= 1, "%s: bad shape N=%d HW=%ld C=%d", what, N,
-              HW, C);
-  const int Cp = cgn_round8(C);
-  for (int i = 0; i < nld; ++i)
-    SEG_REQUIRE(lds[i] % vec == 0 && lds[i] >= Cp,
-                "%s: row pitch %ld not a multiple of %d / below C rounded up to 8 (%d)", what,
-                lds[i], vec, Cp);
-  SEG_REQUIRE(chunks >= 1 && chunks <= CGN_MAX_CHUNKS, "%s: chunks %d out of [1, %d]", what, chunks,
-              CGN_MAX_CHUNKS);
-  SEG_REQUIRE((long)N * C < (1L << 31), "%s: too large", what);
+  // (any C >= 1; every pitch holds C rounded up to 8)
+  const int Cp = cgn_round8(C), need[3] = {Cp, Cp, Cp};
+  if (rows_require(what, dtype, N, HW, C, 1, vec, lds, need, nld, chunks, CGN_MAX_CHUNKS)) return 1;
   *a = PreluArgs();
-  a->N = N; a->HW = HW; a->C = C; a->CV = Cp / vec; a->cvb_log2 = cgn_pick_cvb_log2(a->CV);
-  a->per = cgn_per(HW, chunks, a->cvb_log2);
+  a->N = N; a->HW = HW; a->C = C; a->CV = Cp / vec; a->cvb_log2 = rows_pick_cvb_log2(a->CV, 0);
+  a->per = rows_per(HW, chunks, a->cvb_log2);
   return 0;
 }
 
 static int joint_common(const char* what, int dtype, int N, int H, int W, int C, int d,
                         const long* lds, const int* need, int nld, int chunks, JointArgs* a) {
-  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "%s: bad dtype %d", what, dtype);
-  SEG_REQUIRE(N >= 1 && N <= 65535 && H >= 1 && W >= 1 && C >= CGN_JV && C % CGN_JV == 0 && d >= 1,
-              "%s: bad shape N=%d H=%d W=%d C=%d d=%d", what, N, H, W, C, d);
-  for (int i = 0; i < nld; ++i)
-    SEG_REQUIRE(lds[i] % CGN_JV == 0 && lds[i] >= need[i],
-                "%s: row pitch %ld not a multiple of %d / < %d", what, lds[i], CGN_JV, need[i]);
-  SEG_REQUIRE(chunks >= 1 && chunks <= CGN_MAX_CHUNKS, "%s: chunks %d out of [1, %d]", what, chunks,
-              CGN_MAX_CHUNKS);
-  SEG_REQUIRE((long)H * W < (1L << 31) && (long)H + d < (1L << 30) && (long)W + d < (1L << 30),
-              "%s: too large", what);
+  SEG_REQUIRE(H >= 1 && W >= 1 && d >= 1 && (long)H * W < (1L << 31) && (long)H + d < (1L << 30) &&
+                  (long)W + d < (1L << 30),
+              "%s: bad shape H=%d W=%d d=%d", what, H, W, d);
+  if (rows_require(what, dtype, N, (long)H * W, C, CGN_JV, CGN_JV, lds, need, nld, chunks,
+                   CGN_MAX_CHUNKS))
+    return 1;
   *a = JointArgs();
   a->N = N; a->H = H; a->W = W; a->C = C; a->d = d; a->CV = C / CGN_JV;
-  a->cvb_log2 = cgn_pick_cvb_log2(a->CV);
-  a->per = cgn_per((long)H * W, chunks, a->cvb_log2);
+  a->cvb_log2 = rows_pick_cvb_log2(a->CV, 0);
+  a->per = rows_per((long)H * W, chunks, a->cvb_log2);
   return 0;
 }
 
@@ -244,14 +232,8 @@ static int joint_common(const char* what, int dtype, int N, int H, int W, int C,
 extern "C" int seg_cg_joint_chunks(int N, int H, int W, int C) {
   using namespace seg;
   if (N < 1 || H < 1 || W < 1 || C < CGN_JV || C % CGN_JV != 0) return -1;
-  const int CV = C / CGN_JV, l = cgn_pick_cvb_log2(CV);
-  const long gx = (CV + (1 << l) - 1) >> l, spb = CGN_THREADS >> l, HW = (long)H * W;
-  long c = (2048 + (long)N * gx - 1) / ((long)N * gx);
-  const long cap = (HW + spb - 1) / spb;
-  if (c > cap) c = cap;
-  if (c > CGN_MAX_CHUNKS) c = CGN_MAX_CHUNKS;
-  if (c < 1) c = 1;
-  return (int)c;
+  const int CV = C / CGN_JV, l = rows_pick_cvb_log2(CV, 0);
+  return rows_chunks(N, rows_gx(CV, l), (long)H * W, CGN_THREADS >> l, 2048, CGN_MAX_CHUNKS);
 }
 
 // y [N,H,W,2C] (pitch ldy >= 2C); partial fp32 [chunks * N][2][2C], nullable
@@ -266,7 +248,8 @@ extern "C" int seg_cg_joint_fwd(int dtype, const void* x, long ldx, int N, int H
   SEG_REQUIRE(x != nullptr && y != nullptr && w_loc != nullptr && w_sur != nullptr,
               "cg_joint_fwd: null x / y / weights");
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.wl = w_loc; a.ws = w_sur; a.partial = partial;
-  CGN_LAUNCH(cg_joint_fwd_kernel, a, chunks, stream);
+  SEG_LAUNCH_T(cg_joint_fwd_kernel, rows_grid(a.CV, a.cvb_log2, chunks, N), dim3(CGN_THREADS), 0,
+               stream, a);
   return check_launch("cg_joint_fwd");
 }
 
@@ -284,7 +267,8 @@ extern "C" int seg_bn_prelu_fwd(int dtype, const void* x, long ldx, const float*
   SEG_REQUIRE((scale == nullptr) == (shift == nullptr), "bn_prelu_fwd: scale and shift go together");
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.scale = scale; a.shift = shift; a.alpha = alpha;
   a.partial = partial;
-  CGN_LAUNCH(bn_prelu_fwd_kernel, a, chunks, stream);
+  SEG_LAUNCH_T(bn_prelu_fwd_kernel, rows_grid(a.CV, a.cvb_log2, chunks, N), dim3(CGN_THREADS), 0,
+               stream, a);
   return check_launch("bn_prelu_fwd");
 }
 
@@ -305,6 +289,7 @@ extern "C" int seg_prelu_bwd(int dtype, const void* g_y, long ldgy, const float*
   a.x = x; a.ldx = ldx; a.gy = g_y; a.ldgy = ldgy; a.gpool = g_pool; a.y = g_z; a.ldy = ldgz;
   a.scale = scale; a.shift = shift; a.alpha = alpha; a.partial = partial;
   a.inv_hw = 1.f / (float)HW;
-  CGN_LAUNCH(prelu_bwd_kernel, a, chunks, stream);
+  SEG_LAUNCH_T(prelu_bwd_kernel, rows_grid(a.CV, a.cvb_log2, chunks, N), dim3(CGN_THREADS), 0,
+               stream, a);
   return check_launch("prelu_bwd");
 }

@@ -16,11 +16,11 @@
 // per element, and the per-(n, c) sums live in registers.  A block reduces its rows through LDS
 // in row order and writes one fp32 partial row; the chunks are summed in index order
 // (seg_colsum / the finalize kernel).  No atomics: the same inputs give the same bits.
-#include "common.h"
+#include "rows.h"
 
 namespace seg {
 
-constexpr int CG_THREADS = 256;
+constexpr int CG_THREADS = ROWS_THREADS;
 constexpr int CG_MAX_CHUNKS = 64;
 
 struct ChanGateArgs {
@@ -33,32 +33,6 @@ struct ChanGateArgs {
 };
 
 __device__ __forceinline__ float cg_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
-
-// Sum the K accumulator vectors of the block's rows in row order and write partial[chunk][n].
-// smem: [K][rows][cvb * VEC]
-template <int VEC, int K>
-__device__ __forceinline__ void cg_block_reduce(const ChanGateArgs& a, float* smem,
-                                                const float (&acc)[K][VEC]) {
-  const int tid = threadIdx.x;
-  const int cvb = 1 << a.cvb_log2, spb = CG_THREADS >> a.cvb_log2;
-  const int cx = tid & (cvb - 1), sy = tid >> a.cvb_log2;
-  const int W = cvb * VEC;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    float* mine = smem + ((long)k * spb + sy) * W + cx * VEC;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) mine[e] = acc[k][e];
-  }
-  __syncthreads();
-  for (int i = tid; i < K * W; i += CG_THREADS) {
-    const int k = i / W, e = i - k * W;
-    float tot = 0.f;
-    for (int rr = 0; rr < spb; ++rr) tot += smem[((long)k * spb + rr) * W + e];
-    const int c = blockIdx.x * W + e;
-    if (c < a.C)
-      a.partial[(((long)blockIdx.y * a.N + blockIdx.z) * K + k) * a.C + c] = tot;
-  }
-}
 
 template <typename T>
 __global__ __launch_bounds__(CG_THREADS) void apply_pool_fwd_kernel(const ChanGateArgs a) {
@@ -94,7 +68,8 @@ __global__ __launch_bounds__(CG_THREADS) void apply_pool_fwd_kernel(const ChanGa
       for (int e = 0; e < VEC; ++e) acc[0][e] += f[e];
     }
   }
-  cg_block_reduce<VEC, 1>(a, smem, acc);
+  rows_block_reduce<VEC, 1>(smem, acc, a.cvb_log2, blockIdx.x, a.C,
+                            a.partial + ((long)blockIdx.y * a.N + n) * a.C, 0);
 }
 
 template <typename T>
@@ -170,7 +145,8 @@ __global__ __launch_bounds__(CG_THREADS) void chan_gate_bwd_kernel(const ChanGat
       if (DX != nullptr) stg16(DX + row * a.ldy + c0, Vec<T>::pack(d));
     }
   }
-  cg_block_reduce<VEC, 2>(a, smem, acc);
+  rows_block_reduce<VEC, 2>(smem, acc, a.cvb_log2, blockIdx.x, a.C,
+                            a.partial + ((long)blockIdx.y * a.N + n) * 2 * a.C, a.C);
 }
 
 // partial [chunks][N][2][C] -> da[n][c] = s(1-s) * sum dy*x, dradd[n][c] = sum dy (nullable)
@@ -223,65 +199,24 @@ __global__ __launch_bounds__(CG_THREADS) void bcast_add_kernel(const ChanGateArg
   }
 }
 
-// lanes (16-byte channel vectors) per block row: the power of two <= 32 that wastes the fewest
-// lanes, the widest among equals (a whole wave on contiguous channels where C allows it)
-static int cg_pick_cvb_log2(int CV) {
-  int best = 5;
-  double bu = 0;
-  for (int l = 5; l >= 0; --l) {
-    const int b = 1 << l;
-    const double u = (double)CV / (double)(((CV + b - 1) / b) * b);
-    if (u > bu + 1e-9) { bu = u; best = l; }
-  }
-  return best;
-}
-
 static int cg_common(const char* what, int dtype, int N, long HW, int C, const long* lds, int nld,
                      int chunks, ChanGateArgs* a) {
   const int vec = dtype == DT_BF16 ? 8 : 4;
-  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "%s: bad dtype %d", what, dtype);
-  SEG_REQUIRE(N >= 1 && N <= 65535 && HW >= 1 && C >= vec && C % vec == 0,
-              "%s: bad shape N=%d HW=%ld C=%d", what, N, HW, C);
-  for (int i = 0; i < nld; ++i)
-    SEG_REQUIRE(lds[i] % vec == 0 && lds[i] >= C, "%s: row pitch %ld not a multiple of %d / < C",
-                what, lds[i], vec);
-  SEG_REQUIRE(chunks >= 1 && chunks <= CG_MAX_CHUNKS, "%s: chunks %d out of [1, %d]", what, chunks,
-              CG_MAX_CHUNKS);
-  SEG_REQUIRE((long)N * C < (1L << 31), "%s: too large", what);
+  if (rows_require(what, dtype, N, HW, C, vec, vec, lds, nullptr, nld, chunks, CG_MAX_CHUNKS))
+    return 1;
   *a = ChanGateArgs();
-  a->N = N; a->HW = HW; a->C = C; a->CV = C / vec; a->cvb_log2 = cg_pick_cvb_log2(a->CV);
+  a->N = N; a->HW = HW; a->C = C; a->CV = C / vec; a->cvb_log2 = rows_pick_cvb_log2(a->CV, 0);
   a->chunks = chunks;
   return 0;
 }
 
-static dim3 cg_grid(const ChanGateArgs& a) {
-  const int cvb = 1 << a.cvb_log2;
-  return dim3((a.CV + cvb - 1) / cvb, a.chunks, a.N);
-}
-
 }  // namespace seg
-
-#define CG_LAUNCH(kernel, a, stream)                                                             \
-  do {                                                                                           \
-    if (dtype == DT_BF16)                                                                        \
-      hipLaunchKernelGGL((kernel<bf16_t>), cg_grid(a), dim3(CG_THREADS), 0, (hipStream_t)stream, \
-                         a);                                                                     \
-    else                                                                                         \
-      hipLaunchKernelGGL((kernel<float>), cg_grid(a), dim3(CG_THREADS), 0, (hipStream_t)stream,  \
-                         a);                                                                     \
-  } while (0)
 
 // Pixel chunks per image of the launches below (rows of their partial buffers): enough blocks to
 // fill the device, at least 32 pixels per chunk, at most 64 chunks.
 extern "C" int seg_apply_pool_chunks(int N, long HW, int C) {
   if (N < 1 || HW < 1 || C < 1) return -1;
-  const long gx = (C + 127) / 128;
-  long c = (1024 + (long)N * gx - 1) / ((long)N * gx);
-  const long cap = (HW + 31) / 32;
-  if (c > cap) c = cap;
-  if (c > seg::CG_MAX_CHUNKS) c = seg::CG_MAX_CHUNKS;
-  if (c < 1) c = 1;
-  return (int)c;
+  return seg::rows_chunks(N, (C + 127) / 128, HW, 32, 1024, seg::CG_MAX_CHUNKS);
 }
 
 extern "C" int seg_apply_pool_fwd(int dtype, const void* x, long ldx, int pro_mode,
@@ -299,7 +234,8 @@ extern "C" int seg_apply_pool_fwd(int dtype, const void* x, long ldx, int pro_mo
               "apply_pool_fwd: affine prologue without scale / shift");
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.mode = pro_mode; a.scale = pro_scale;
   a.shift = pro_shift; a.partial = partial;
-  CG_LAUNCH(apply_pool_fwd_kernel, a, stream);
+  SEG_LAUNCH_T(apply_pool_fwd_kernel, rows_grid(a.CV, a.cvb_log2, chunks, N), dim3(CG_THREADS), 0,
+               stream, a);
   return check_launch("apply_pool_fwd");
 }
 
@@ -314,7 +250,8 @@ extern "C" int seg_chan_gate_fwd(int dtype, const void* x, long ldx, const float
   SEG_REQUIRE(identity == 0 || identity == 1, "chan_gate_fwd: identity must be 0 or 1");
   a.x = x; a.ldx = ldx; a.a = a_pre; a.identity = identity; a.r = r; a.ldr = ldr; a.radd = radd;
   a.y = y; a.ldy = ldy;
-  CG_LAUNCH(chan_gate_fwd_kernel, a, stream);
+  SEG_LAUNCH_T(chan_gate_fwd_kernel, rows_grid(a.CV, a.cvb_log2, chunks, N), dim3(CG_THREADS), 0,
+               stream, a);
   return check_launch("chan_gate_fwd");
 }
 
@@ -331,7 +268,8 @@ extern "C" int seg_chan_gate_bwd(int dtype, const void* dy, long lddy, const voi
   SEG_REQUIRE(identity == 0 || identity == 1, "chan_gate_bwd: identity must be 0 or 1");
   a.dy = dy; a.lddy = lddy; a.x = x; a.ldx = ldx; a.a = a_pre; a.identity = identity; a.y = dx;
   a.ldy = lddx; a.partial = partial;
-  CG_LAUNCH(chan_gate_bwd_kernel, a, stream);
+  SEG_LAUNCH_T(chan_gate_bwd_kernel, rows_grid(a.CV, a.cvb_log2, chunks, N), dim3(CG_THREADS), 0,
+               stream, a);
   return check_launch("chan_gate_bwd");
 }
 
@@ -359,6 +297,7 @@ extern "C" int seg_bcast_add(int dtype, const void* g, long ldg, const float* v,
   if (cg_common("bcast_add", dtype, N, HW, C, lds, 2, chunks, &a)) return 1;
   SEG_REQUIRE(y != nullptr && v != nullptr, "bcast_add: null y / v");
   a.x = g; a.ldx = ldg; a.a = v; a.vscale = scale; a.y = y; a.ldy = ldy;
-  CG_LAUNCH(bcast_add_kernel, a, stream);
+  SEG_LAUNCH_T(bcast_add_kernel, rows_grid(a.CV, a.cvb_log2, chunks, N), dim3(CG_THREADS), 0,
+               stream, a);
   return check_launch("bcast_add");
 }

@@ -265,3 +265,24 @@ int check_launch(const char* what);
               "%s: %ld x %ld indices are beyond the exact range of the float-reciprocal index "  \
               "division (at most %ld quotients above 2^24 indices, and 2^31 indices)",           \
               what, (long)(count), (long)(d), seg::FAST_DIV_MAX_QUOT)
+
+// kernel<bf16_t, extra...> or kernel<float, extra...> by the `dtype` in scope at the call:
+//   SEG_LAUNCH_T(kernel, grid, block, lds_bytes, stream, args...)
+//   SEG_LAUNCH_T((kernel, true), grid, block, lds_bytes, stream, args...)  (more template arguments)
+#define SEG_LAUNCH_T(kernel, grid, block, lds_bytes, stream, ...)                               \
+  do {                                                                                          \
+    if (dtype == seg::DT_BF16)                                                                  \
+      hipLaunchKernelGGL((SEG_KERNEL_T_(seg::bf16_t, SEG_UNPAREN_(kernel))), grid, block,       \
+                         lds_bytes, (hipStream_t)(stream), __VA_ARGS__);                        \
+    else                                                                                        \
+      hipLaunchKernelGGL((SEG_KERNEL_T_(float, SEG_UNPAREN_(kernel))), grid, block, lds_bytes,  \
+                         (hipStream_t)(stream), __VA_ARGS__);                                   \
+  } while (0)
+#define SEG_KERNEL_T_(T, ...) SEG_KERNEL_T2_(T, __VA_ARGS__)
+#define SEG_KERNEL_T2_(T, k, ...) k<T, ##__VA_ARGS__>
+// (k, x) -> k, x and k -> k: SEG_PAREN_ eats a parenthesised list, the paste erases what is left
+#define SEG_UNPAREN_(x) SEG_UNPAREN2_(SEG_PAREN_ x)
+#define SEG_UNPAREN2_(...) SEG_UNPAREN3_(__VA_ARGS__)
+#define SEG_UNPAREN3_(...) SEG_ERASE_##__VA_ARGS__
+#define SEG_PAREN_(...) SEG_PAREN_ __VA_ARGS__
+#define SEG_ERASE_SEG_PAREN_

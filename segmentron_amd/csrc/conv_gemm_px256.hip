@@ -264,10 +264,7 @@ int launch_conv_gemm_px256(int dtype, ConvGemmArgs a, hipStream_t stream) {
   a.tiles_m = px256_tiles_m(a.M);
   a.tiles_n = (a.O + PX_BN - 1) / PX_BN;
   const dim3 grid(a.tiles_m * a.tiles_n), block(GEMM_THREADS);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((conv_gemm_px256_kernel<bf16_t>), grid, block, 0, stream, a);
-  else
-    hipLaunchKernelGGL((conv_gemm_px256_kernel<float>), grid, block, 0, stream, a);
+  SEG_LAUNCH_T(conv_gemm_px256_kernel, grid, block, 0, stream, a);
   return check_launch("conv_gemm_fwd (px256)");
 }
 

@@ -25,6 +25,7 @@
 // STORED (after `add`, after the rounding to bf16), accumulated in registers over the block's
 // tiles and folded lanes -> waves in a fixed order.  No atomics anywhere.
 #include "conv_gemm.h"
+#include "rows.h"
 
 namespace seg {
 
@@ -582,11 +583,6 @@ static int line_wgrad_grid(int dtype, long P, int C) {
   return (int)(nt < cap ? nt : cap);
 }
 
-static int tail_grid(long items) {
-  const long nb = (items + ST_THREADS - 1) / ST_THREADS;
-  return (int)(nb < ST_MAX_BLOCKS ? nb : ST_MAX_BLOCKS);
-}
-
 template <typename T, int C>
 static void launch_line(const LineArgs& a, int grid, hipStream_t s) {
   const bool pro = a.pro_mode != PRO_NONE, st = a.stat != nullptr;
@@ -741,7 +737,7 @@ extern "C" int seg_ssnbt_tail_geom(int dtype, long P, int C, int what) {
       P >= (1L << 31))
     return -1;
   const long items = P * (C / 2 / (dtype == DT_BF16 ? 8 : 4));
-  const int grid = tail_grid(items);
+  const int grid = grid_1d(items, ST_THREADS, ST_MAX_BLOCKS);
   switch (what) {
     case 0: return ST_THREADS;
     case 1: return grid;
@@ -753,13 +749,11 @@ extern "C" int seg_ssnbt_tail_geom(int dtype, long P, int C, int what) {
 static int tail_common(const char* what, int dtype, long P, int C, const long* lds, int nld,
                        seg::TailArgs* a) {
   using namespace seg;
-  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "%s: bad dtype %d", what, dtype);
-  SEG_REQUIRE((C == 32 || C == 64 || C == 128) && P >= 1 && P < (1L << 31), "%s: bad P=%ld C=%d",
-              what, P, C);
+  SEG_REQUIRE((C == 32 || C == 64 || C == 128) && P < (1L << 31), "%s: bad P=%ld C=%d", what, P, C);
   const int vec = dtype == DT_BF16 ? 8 : 4;
-  for (int i = 0; i < nld; ++i)
-    SEG_REQUIRE(lds[i] % vec == 0 && lds[i] >= (i < 2 ? C / 2 : C),
-                "%s: row pitch %ld too small or not a multiple of %d", what, lds[i], vec);
+  const int need[5] = {C / 2, C / 2, C, C, C};  // (the two halves, then whole rows)
+  // (one "image" of P pixels, no chunks)
+  if (rows_require(what, dtype, 1, P, C, vec, vec, lds, need, nld, 1, 1)) return 1;
   *a = TailArgs();
   a->C = C; a->vpp = C / 2 / vec; a->items = P * a->vpp;
   return 0;
@@ -776,11 +770,8 @@ extern "C" int seg_ssnbt_tail_fwd(int dtype, const void* y0, long ldy0, const fl
   SEG_REQUIRE(y0 && y1 && s0 && t0 && s1 && t1 && x && out, "ssnbt_tail_fwd: null pointer");
   a.y0 = y0; a.ldy0 = ldy0; a.y1 = y1; a.ldy1 = ldy1; a.s0 = s0; a.t0 = t0; a.s1 = s1; a.t1 = t1;
   a.x = x; a.ldx = ldx; a.out = out; a.ldout = ldout;
-  const dim3 grid(tail_grid(a.items));
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((ssnbt_tail_fwd_kernel<bf16_t>), grid, dim3(ST_THREADS), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((ssnbt_tail_fwd_kernel<float>), grid, dim3(ST_THREADS), 0, (hipStream_t)stream, a);
+  const dim3 grid(grid_1d(a.items, ST_THREADS, ST_MAX_BLOCKS));
+  SEG_LAUNCH_T(ssnbt_tail_fwd_kernel, grid, dim3(ST_THREADS), 0, stream, a);
   return check_launch("ssnbt_tail_fwd");
 }
 
@@ -792,10 +783,7 @@ extern "C" int seg_ssnbt_tail_bwd(int dtype, const void* gout, long ldgout, cons
   if (tail_common("ssnbt_tail_bwd", dtype, P, C, lds, 5, &a)) return 1;
   SEG_REQUIRE(gout && out && gm, "ssnbt_tail_bwd: null pointer");
   a.gout = gout; a.ldgout = ldgout; a.outr = out; a.ldout = ldout; a.gm = gm; a.ldgm = ldgm;
-  const dim3 grid(tail_grid(a.items));
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((ssnbt_tail_bwd_kernel<bf16_t>), grid, dim3(ST_THREADS), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((ssnbt_tail_bwd_kernel<float>), grid, dim3(ST_THREADS), 0, (hipStream_t)stream, a);
+  const dim3 grid(grid_1d(a.items, ST_THREADS, ST_MAX_BLOCKS));
+  SEG_LAUNCH_T(ssnbt_tail_bwd_kernel, grid, dim3(ST_THREADS), 0, stream, a);
   return check_launch("ssnbt_tail_bwd");
 }

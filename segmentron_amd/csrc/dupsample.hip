@@ -333,12 +333,8 @@ extern "C" int seg_dup_ce_fwd(int dtype, const void* lo, long ld, int N, int h, 
               "dup_ce_fwd: null or misaligned pointer");
   a.lo = lo;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((dup_ce_fwd_kernel<bf16_t>), dim3((unsigned)blocks), dim3(DUP_THREADS), lds,
-                       st, a, target, ignore_index, ws);
-  else
-    hipLaunchKernelGGL((dup_ce_fwd_kernel<float>), dim3((unsigned)blocks), dim3(DUP_THREADS), lds,
-                       st, a, target, ignore_index, ws);
+  SEG_LAUNCH_T(dup_ce_fwd_kernel, dim3((unsigned)blocks), dim3(DUP_THREADS), lds, st, a, target,
+               ignore_index, ws);
   hipLaunchKernelGGL(dup_ce_finalize_kernel, dim3(1), dim3(256), 0, st, ws, (int)blocks, loss_out);
   return check_launch("dup_ce_fwd");
 }
@@ -373,12 +369,7 @@ extern "C" int seg_dup_to_nchw(int dtype, const void* lo, long ld, int N, int h,
   SEG_REQUIRE(lo && out && dup_aligned(lo), "dup_to_nchw: null or misaligned pointer");
   a.lo = lo;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((dup_to_nchw_kernel<bf16_t>), dim3((unsigned)blocks), dim3(DUP_THREADS), lds,
-                       st, a, out);
-  else
-    hipLaunchKernelGGL((dup_to_nchw_kernel<float>), dim3((unsigned)blocks), dim3(DUP_THREADS), lds,
-                       st, a, out);
+  SEG_LAUNCH_T(dup_to_nchw_kernel, dim3((unsigned)blocks), dim3(DUP_THREADS), lds, st, a, out);
   return check_launch("dup_to_nchw");
 }
 

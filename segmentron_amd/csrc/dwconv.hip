@@ -15,7 +15,7 @@
 // pixel strips; a strip is TW=4 consecutive output pixels of one row.  blockIdx.x tiles the
 // channel vectors, blockIdx.y the strips (grid-stride), one row of statistics partials per
 // blockIdx.y (deterministic: LDS tree over the strips of a block, fp64 finish in bn_finalize).
-#include "common.h"
+#include "rows.h"
 #include "dwconv.h"
 #include <cstdlib>
 #include <type_traits>
@@ -438,21 +438,10 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_bwd_fused_kernel(const DwBw
   }
 }
 
-static int pick_cvb_log2(int CV) {
-  // largest utilisation among 32/16/8 channel vectors per block; ties -> wider
-  int best = 5;
-  double bu = 0;
-  for (int l = 5; l >= 3; --l) {
-    const int b = 1 << l;
-    const double u = (double)CV / (double)(((CV + b - 1) / b) * b);
-    if (u > bu + 1e-9) { bu = u; best = l; }
-  }
-  return best;
-}
 // strip launches: blocks along the channel vectors
 static int strip_gx(int CV, int& cvb_log2) {
-  cvb_log2 = pick_cvb_log2(CV);
-  return (CV + (1 << cvb_log2) - 1) >> cvb_log2;
+  cvb_log2 = rows_pick_cvb_log2(CV, 3);  // 32 / 16 / 8 channel vectors per block
+  return rows_gx(CV, cvb_log2);
 }
 
 // The kernel family of a depthwise 3x3 launch: the ONLY statement of that policy in the library
@@ -618,10 +607,7 @@ extern "C" int seg_dwconv3x3_wgrad(int dtype, const void* x, long ldx, int N, in
   const dim3 grid(strip_gx(a.CV, a.cvb_log2), grid_y);
   const size_t lds = (size_t)DW_THREADS * 3 * vec * sizeof(float);
   SEG_REQUIRE_FAST_DIV("dwconv3x3_wgrad", (long)N * Ho, (Wo + DW_TW - 1) / DW_TW);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((dwconv_wgrad_kernel<bf16_t>), grid, dim3(DW_THREADS), lds, st, a);
-  else
-    hipLaunchKernelGGL((dwconv_wgrad_kernel<float>), grid, dim3(DW_THREADS), lds, st, a);
+  SEG_LAUNCH_T(dwconv_wgrad_kernel, grid, dim3(DW_THREADS), lds, st, a);
   return check_launch("dwconv3x3_wgrad");
 }
 
@@ -681,10 +667,7 @@ static int dw_bwd_fused(const char* name, int dtype, const void* dy, long lddy, 
   SEG_REQUIRE((long)N * H * W * lddy < (1L << 31), "%s: 32-bit offsets", name);
   const dim3 grid(strip_gx(a.CV, a.cvb_log2), grid_y);
   const size_t lds = (size_t)DW_THREADS * 3 * vec * sizeof(float);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((dwconv_bwd_fused_kernel<bf16_t>), grid, dim3(DW_THREADS), lds, st, a);
-  else
-    hipLaunchKernelGGL((dwconv_bwd_fused_kernel<float>), grid, dim3(DW_THREADS), lds, st, a);
+  SEG_LAUNCH_T(dwconv_bwd_fused_kernel, grid, dim3(DW_THREADS), lds, st, a);
   return check_launch(name);
 }
 }  // namespace seg

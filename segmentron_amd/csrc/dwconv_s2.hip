@@ -269,11 +269,6 @@ extern "C" int seg_dwconv3x3_s2_bwd_fused(int dtype, const void* dy, long lddy, 
   a.tiles_h = (H + S2_TH - 1) / S2_TH; a.tiles_w = (W + S2_TW - 1) / S2_TW;
   a.ntiles = N * a.tiles_h * a.tiles_w;
   const dim3 grid((a.CV + S2_CVB - 1) / S2_CVB, grid_y);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((dwconv_bwd_s2_kernel<bf16_t>), grid, dim3(S2_THREADS), 0,
-                       (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((dwconv_bwd_s2_kernel<float>), grid, dim3(S2_THREADS), 0,
-                       (hipStream_t)stream, a);
+  SEG_LAUNCH_T(dwconv_bwd_s2_kernel, grid, dim3(S2_THREADS), 0, stream, a);
   return check_launch("dwconv3x3_s2_bwd_fused");
 }

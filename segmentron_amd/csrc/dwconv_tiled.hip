@@ -1173,10 +1173,7 @@ int launch_dw_tiled(int dtype, const void* x, long ldx, int N, int H, int W, int
   a.ldx = ldx; a.ldy = ldy; a.lddy = 0; a.pro_mode = pro_mode;
   const dim3 grid((a.CV + LT_CVB - 1) / LT_CVB, grid_y);
   const size_t lds = tiled_lds<2>(dtype, a.nb, a.nc);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((dwconv_tiled_kernel<bf16_t, 2>), grid, dim3(LT_THREADS), lds, st, a);
-  else
-    hipLaunchKernelGGL((dwconv_tiled_kernel<float, 2>), grid, dim3(LT_THREADS), lds, st, a);
+  SEG_LAUNCH_T((dwconv_tiled_kernel, 2), grid, dim3(LT_THREADS), lds, st, a);
   return check_launch("dwconv3x3 (tiled)");
 }
 

@@ -17,7 +17,7 @@
 //                          the backward gathers the <= 4 outputs that read an input pixel.
 //   seg_bn_add_prelu_*     y = prelu(a * sa + ta + b * sb + tb, alpha) and its mask / dalpha pass:
 //                          the EESP tail and the DownSampler tail.
-// The pyramid and the tails use the launch geometry of csrc/cgnet.hip (cgn_rows.h): no atomics, fp32
+// The pyramid and the tails use the launch geometry of csrc/cgnet.hip (rows.h): no atomics, fp32
 // partial rows per (chunk, image) summed in index order, the same bits on every launch, and an
 // image never reaches another image's outputs or partial rows.
 #include "cgn_rows.h"
@@ -114,8 +114,8 @@ __global__ __launch_bounds__(CGN_THREADS) void eesp_pyr_fwd_kernel(const PyrArgs
   // partial[row][2][4n]: k = stat * 4 + branch at offset k * n
   if (a.partial != nullptr) {
     __syncthreads();  // (the weights are read until the last pixel; the reduce reuses their LDS)
-    cgn_block_reduce<V, 8>(smem, acc, a.cvb_log2, a.n,
-                           a.partial + ((long)blockIdx.y * a.N + img_n) * 8 * a.n, a.n);
+    rows_block_reduce<V, 8>(smem, acc, a.cvb_log2, blockIdx.x, a.n,
+                            a.partial + ((long)blockIdx.y * a.N + img_n) * 8 * a.n, a.n);
   }
 }
 
@@ -267,8 +267,8 @@ __global__ __launch_bounds__(CGN_THREADS) void bn_add_prelu_kernel(const AddPrel
     }
   }
   if (BWD)
-    cgn_block_reduce<VEC, 1>(smem, acc, a.cvb_log2, a.C,
-                             a.partial + ((long)blockIdx.y * a.N + n) * a.C, 0);
+    rows_block_reduce<VEC, 1>(smem, acc, a.cvb_log2, blockIdx.x, a.C,
+                              a.partial + ((long)blockIdx.y * a.N + n) * a.C, 0);
 }
 
 static int pyr_geometry(const char* what, int dtype, int N, int H, int W, int n, const int* d,
@@ -305,31 +305,15 @@ static int flat_common(const char* what, int dtype, long rows, int C, const long
 static int add_prelu_common(const char* what, int dtype, int N, long HW, int C, const long* lds,
                             int nld, int chunks, AddPreluArgs* a) {
   const int vec = dtype == DT_BF16 ? 8 : 4;
-  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "%s: bad dtype %d", what, dtype);
-  SEG_REQUIRE(N >= 1 && N <= 65535 && HW >= 1 && C >= vec && C % vec == 0,
-              "%s: bad shape N=%d HW=%ld C=%d (C a multiple of %d)", what, N, HW, C, vec);
-  for (int i = 0; i < nld; ++i)
-    SEG_REQUIRE(lds[i] % vec == 0 && lds[i] >= C, "%s: row pitch %ld not a multiple of %d / < %d",
-                what, lds[i], vec, C);
-  SEG_REQUIRE(chunks >= 1 && chunks <= CGN_MAX_CHUNKS, "%s: chunks %d out of [1, %d]", what, chunks,
-              CGN_MAX_CHUNKS);
-  SEG_REQUIRE((long)N * C < (1L << 31), "%s: too large", what);
+  if (rows_require(what, dtype, N, HW, C, vec, vec, lds, nullptr, nld, chunks, CGN_MAX_CHUNKS))
+    return 1;
   *a = AddPreluArgs();
-  a->N = N; a->HW = HW; a->C = C; a->CV = C / vec; a->cvb_log2 = cgn_pick_cvb_log2(a->CV);
-  a->per = cgn_per(HW, chunks, a->cvb_log2);
+  a->N = N; a->HW = HW; a->C = C; a->CV = C / vec; a->cvb_log2 = rows_pick_cvb_log2(a->CV, 0);
+  a->per = rows_per(HW, chunks, a->cvb_log2);
   return 0;
 }
 
 }  // namespace seg
-
-#define FLAT_LAUNCH(kernel, a, stream)                                                        \
-  do {                                                                                        \
-    const dim3 grid((unsigned)((a.total + 255) / 256));                                       \
-    if (dtype == DT_BF16)                                                                     \
-      hipLaunchKernelGGL((kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, a);       \
-    else                                                                                      \
-      hipLaunchKernelGGL((kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, a);        \
-  } while (0)
 
 // Pixel chunks per image of the pyramid launch (rows of its partial buffer per image), over the
 // OUTPUT pixels: about 2048 blocks, at least one block row of pixels per chunk, at most 256.
@@ -337,14 +321,8 @@ extern "C" int seg_eesp_pyr_chunks(int N, int H, int W, int n, int stride) {
   using namespace seg;
   if (N < 1 || H < 1 || W < 1 || n < 8 || n % 8 != 0 || (stride != 1 && stride != 2)) return -1;
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  const int CV = n / CGN_JV, l = cgn_pick_cvb_log2(CV);
-  const long gx = (CV + (1 << l) - 1) >> l, spb = CGN_THREADS >> l, HW = (long)Ho * Wo;
-  long c = (2048 + (long)N * gx - 1) / ((long)N * gx);
-  const long cap = (HW + spb - 1) / spb;
-  if (c > cap) c = cap;
-  if (c > CGN_MAX_CHUNKS) c = CGN_MAX_CHUNKS;
-  if (c < 1) c = 1;
-  return (int)c;
+  const int CV = n / CGN_JV, l = rows_pick_cvb_log2(CV, 0);
+  return rows_chunks(N, rows_gx(CV, l), (long)Ho * Wo, CGN_THREADS >> l, 2048, CGN_MAX_CHUNKS);
 }
 
 // y [N,Ho,Wo,4n] (pitch ldy >= 4n), Ho = (H-1)/stride + 1; partial fp32 [chunks * N][2][4n], nullable
@@ -369,18 +347,13 @@ extern "C" int seg_eesp_pyr_fwd(int dtype, const void* x, long ldx, int N, int H
   a.N = N; a.H = H; a.W = W; a.n = n; a.s = stride;
   a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1;
   for (int j = 0; j < 4; ++j) a.d[j] = d[j];
-  a.CV = n / CGN_JV; a.cvb_log2 = cgn_pick_cvb_log2(a.CV);
-  a.per = cgn_per((long)a.Ho * a.Wo, chunks, a.cvb_log2);
+  a.CV = n / CGN_JV; a.cvb_log2 = rows_pick_cvb_log2(a.CV, 0);
+  a.per = rows_per((long)a.Ho * a.Wo, chunks, a.cvb_log2);
   const int fresh = 1 | (d[1] != d[0]) << 1 | (d[2] != d[1]) << 2 | (d[3] != d[2]) << 3;
-  const dim3 grid = cgn_grid(a.CV, a.cvb_log2, chunks, a.N);
-#define PYR_CASE(F)                                                                             \
-  case F:                                                                                       \
-    if (dtype == DT_BF16)                                                                       \
-      hipLaunchKernelGGL((eesp_pyr_fwd_kernel<bf16_t, F>), grid, dim3(CGN_THREADS), 0,          \
-                         (hipStream_t)stream, a);                                               \
-    else                                                                                        \
-      hipLaunchKernelGGL((eesp_pyr_fwd_kernel<float, F>), grid, dim3(CGN_THREADS), 0,           \
-                         (hipStream_t)stream, a);                                               \
+  const dim3 grid = rows_grid(a.CV, a.cvb_log2, chunks, a.N);
+#define PYR_CASE(F)                                                                          \
+  case F:                                                                                    \
+    SEG_LAUNCH_T((eesp_pyr_fwd_kernel, F), grid, dim3(CGN_THREADS), 0, stream, a);           \
     break;
   switch (fresh) {
     PYR_CASE(1) PYR_CASE(3) PYR_CASE(5) PYR_CASE(7) PYR_CASE(9) PYR_CASE(11) PYR_CASE(13)
@@ -400,7 +373,8 @@ extern "C" int seg_eesp_suffix_sum(int dtype, const void* g, long ldg, void* s, 
   if (flat_common("eesp_suffix_sum", dtype, rows, n, lda, need, 2, &a)) return 1;
   SEG_REQUIRE(g != nullptr && s != nullptr, "eesp_suffix_sum: null g / s");
   a.x = g; a.ldx = ldg; a.y = s; a.ldy = lds; a.n = n;
-  FLAT_LAUNCH(eesp_suffix_sum_kernel, a, stream);
+  SEG_LAUNCH_T(eesp_suffix_sum_kernel, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0,
+               stream, a);
   return check_launch("eesp_suffix_sum");
 }
 
@@ -416,7 +390,8 @@ extern "C" int seg_avgpool3x3s2_fwd(int dtype, const void* x, long ldx, int N, i
   if (flat_common("avgpool3x3s2_fwd", dtype, (long)N * Ho * Wo, C, lda, need, 2, &a)) return 1;
   SEG_REQUIRE(x != nullptr && y != nullptr, "avgpool3x3s2_fwd: null x / y");
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.N = N; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
-  FLAT_LAUNCH(avgpool3x3s2_fwd_kernel, a, stream);
+  SEG_LAUNCH_T(avgpool3x3s2_fwd_kernel, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0,
+               stream, a);
   return check_launch("avgpool3x3s2_fwd");
 }
 
@@ -432,20 +407,10 @@ extern "C" int seg_avgpool3x3s2_bwd(int dtype, const void* gy, long ldgy, int N,
   SEG_REQUIRE(gy != nullptr && gx != nullptr, "avgpool3x3s2_bwd: null gy / gx");
   a.x = gy; a.ldx = ldgy; a.y = gx; a.ldy = ldgx; a.N = N; a.H = H; a.W = W;
   a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1;
-  FLAT_LAUNCH(avgpool3x3s2_bwd_kernel, a, stream);
+  SEG_LAUNCH_T(avgpool3x3s2_bwd_kernel, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0,
+               stream, a);
   return check_launch("avgpool3x3s2_bwd");
 }
-
-#define ADD_PRELU_LAUNCH(BWD, a, chunks, stream)                                                \
-  do {                                                                                          \
-    const dim3 grid = cgn_grid(a.CV, a.cvb_log2, chunks, a.N);                                  \
-    if (dtype == DT_BF16)                                                                       \
-      hipLaunchKernelGGL((bn_add_prelu_kernel<bf16_t, BWD>), grid, dim3(CGN_THREADS), 0,        \
-                         (hipStream_t)stream, a);                                               \
-    else                                                                                        \
-      hipLaunchKernelGGL((bn_add_prelu_kernel<float, BWD>), grid, dim3(CGN_THREADS), 0,         \
-                         (hipStream_t)stream, a);                                               \
-  } while (0)
 
 // sa / ta and sb / tb each nullable as a pair: that operand is plain
 extern "C" int seg_bn_add_prelu_fwd(int dtype, const void* a_, long lda, const float* sa,
@@ -462,7 +427,8 @@ extern "C" int seg_bn_add_prelu_fwd(int dtype, const void* a_, long lda, const f
               "bn_add_prelu_fwd: scale and shift go together");
   a.a = a_; a.lda = lda; a.b = b_; a.ldb = ldb; a.y = y; a.ldy = ldy;
   a.sa = sa; a.ta = ta; a.sb = sb; a.tb = tb; a.alpha = alpha;
-  ADD_PRELU_LAUNCH(false, a, chunks, stream);
+  SEG_LAUNCH_T((bn_add_prelu_kernel, false), rows_grid(a.CV, a.cvb_log2, chunks, N),
+               dim3(CGN_THREADS), 0, stream, a);
   return check_launch("bn_add_prelu_fwd");
 }
 
@@ -484,6 +450,7 @@ extern "C" int seg_bn_add_prelu_bwd(int dtype, const void* g, long ldg, const vo
               "bn_add_prelu_bwd: scale and shift go together");
   a.a = a_; a.lda = lda; a.b = b_; a.ldb = ldb; a.g = g; a.ldg = ldg; a.y = g_z; a.ldy = ldgz;
   a.sa = sa; a.ta = ta; a.sb = sb; a.tb = tb; a.alpha = alpha; a.partial = partial;
-  ADD_PRELU_LAUNCH(true, a, chunks, stream);
+  SEG_LAUNCH_T((bn_add_prelu_kernel, true), rows_grid(a.CV, a.cvb_log2, chunks, N),
+               dim3(CGN_THREADS), 0, stream, a);
   return check_launch("bn_add_prelu_bwd");
 }

@@ -19,7 +19,7 @@
 //                       sa[p] = sigmoid(w_sa * mean_c(sl*L + tl)), align_corners bilinear.
 //   seg_meu_bwd_low     the gradient at bn_low's output and the rows of da, d w_sa and bn_low.
 //   seg_meu_bwd_high    the gradient at bn_high's output, a gather, and bn_high's rows.
-// All use the launch geometry of cgn_rows.h with 4-channel vectors (16 B of fp32, 8 B of bf16): no
+// All use the launch geometry of rows.h with 4-channel vectors (16 B of fp32, 8 B of bf16): no
 // atomics, fp32 partial rows per (chunk, image) summed in index order, the same bits on every launch,
 // and an image never reaches another image's outputs or partial rows.
 #include "cgn_rows.h"
@@ -114,8 +114,8 @@ __global__ __launch_bounds__(CGN_THREADS) void fpe_stage_fwd_kernel(const FpeFwd
     }
   }
   if (a.partial != nullptr)
-    cgn_block_reduce<V, 2>(smem, acc, a.cvb_log2, a.n,
-                           a.partial + ((long)blockIdx.y * a.N + img) * 2 * a.n, a.n);
+    rows_block_reduce<V, 2>(smem, acc, a.cvb_log2, blockIdx.x, a.n,
+                            a.partial + ((long)blockIdx.y * a.N + img) * 2 * a.n, a.n);
 }
 
 // ------------------------------------------------------------------------------- flat slice passes
@@ -264,11 +264,12 @@ __global__ __launch_bounds__(CGN_THREADS) void fpe_stage_bwd_kernel(const FpeBwd
   }
   const long row = (long)blockIdx.y * a.N + img;
   if (MODE != 2) {
-    cgn_block_reduce<V, 9>(smem, aw, a.cvb_log2, a.n, a.pw + row * 9 * a.n, a.n);
-    cgn_block_reduce<V, 2>(smem, apa, a.cvb_log2, a.n, a.pa + row * 2 * a.pa_pitch + a.pa_col,
-                           a.pa_pitch);
+    rows_block_reduce<V, 9>(smem, aw, a.cvb_log2, blockIdx.x, a.n, a.pw + row * 9 * a.n, a.n);
+    rows_block_reduce<V, 2>(smem, apa, a.cvb_log2, blockIdx.x, a.n,
+                            a.pa + row * 2 * a.pa_pitch + a.pa_col, a.pa_pitch);
   }
-  if (MODE != 0) cgn_block_reduce<V, 2>(smem, apb, a.cvb_log2, a.n, a.pb + row * 2 * a.n, a.n);
+  if (MODE != 0) rows_block_reduce<V, 2>(smem, apb, a.cvb_log2, blockIdx.x, a.n,
+                                         a.pb + row * 2 * a.n, a.n);
 }
 
 // ------------------------------------------------------------------------------- MEU
@@ -391,8 +392,8 @@ __global__ __launch_bounds__(CGN_THREADS) void meu_low_kernel(const MeuArgs a) {
   }
   if (BWD) {
     const long row = (long)blockIdx.y * a.N + img;
-    cgn_block_reduce<V, 2>(smem, acc1, a.cvb_log2, a.C, a.p1 + row * 2 * a.C, a.C);
-    cgn_block_reduce<V, 2>(smem, acc2, a.cvb_log2, a.C, a.p2 + row * 2 * a.C, a.C);
+    rows_block_reduce<V, 2>(smem, acc1, a.cvb_log2, blockIdx.x, a.C, a.p1 + row * 2 * a.C, a.C);
+    rows_block_reduce<V, 2>(smem, acc2, a.cvb_log2, blockIdx.x, a.C, a.p2 + row * 2 * a.C, a.C);
   }
 }
 
@@ -456,54 +457,46 @@ __global__ __launch_bounds__(CGN_THREADS) void meu_high_bwd_kernel(const MeuArgs
       HVec<T>::store(Oimg + q * a.ldo, d);
     }
   }
-  cgn_block_reduce<V, 2>(smem, acc, a.cvb_log2, a.C,
-                         a.p2 + ((long)blockIdx.y * a.N + img) * 2 * a.C, a.C);
+  rows_block_reduce<V, 2>(smem, acc, a.cvb_log2, blockIdx.x, a.C,
+                          a.p2 + ((long)blockIdx.y * a.N + img) * 2 * a.C, a.C);
 }
 
 // ------------------------------------------------------------------------------- host side
 // chunks per image: about 2048 blocks, at least one block row of pixels per chunk, at most 256
 static int fpe_chunks(int N, long HW, int CV, int cvb_log2) {
-  const long gx = (CV + (1 << cvb_log2) - 1) >> cvb_log2, spb = CGN_THREADS >> cvb_log2;
-  long c = (2048 + (long)N * gx - 1) / ((long)N * gx);
-  const long cap = (HW + spb - 1) / spb;
-  if (c > cap) c = cap;
-  if (c > CGN_MAX_CHUNKS) c = CGN_MAX_CHUNKS;
-  if (c < 1) c = 1;
-  return (int)c;
-}
-
-static int meu_lanes_log2(int CV) {
-  int l = 0;
-  while ((1 << l) < CV) ++l;
-  return l;
-}
-
-static int fpe_geometry(const char* what, int dtype, int N, int H, int W, int n, int dil) {
-  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "%s: bad dtype %d", what, dtype);
-  SEG_REQUIRE(N >= 1 && N <= 65535 && H >= 1 && W >= 1 && (long)H * W < (1L << 31),
-              "%s: bad shape N=%d H=%d W=%d", what, N, H, W);
-  SEG_REQUIRE(n >= 4 && n % 4 == 0 && n <= FPE_MAX_N,
-              "%s: n=%d is not a positive multiple of 4 up to %d", what, n, FPE_MAX_N);
-  SEG_REQUIRE(dil >= 1 && dil <= FPE_MAX_DIL, "%s: dilation %d not in 1..%d", what, dil,
-              FPE_MAX_DIL);
-  return 0;
+  return rows_chunks(N, rows_gx(CV, cvb_log2), HW, CGN_THREADS >> cvb_log2, 2048, CGN_MAX_CHUNKS);
 }
 
 static int fpe_rows_ok(const char* what, int rows, int N, int* chunks) {
-  SEG_REQUIRE(rows >= N && rows % N == 0 && rows / N <= CGN_MAX_CHUNKS,
+  SEG_REQUIRE(N >= 1 && rows >= N && rows % N == 0 && rows / N <= CGN_MAX_CHUNKS,
               "%s: %d partial rows are not 1..%d chunks of %d images", what, rows, CGN_MAX_CHUNKS, N);
   *chunks = rows / N;
   return 0;
 }
 
-static int meu_geometry(const char* what, int dtype, int N, int h, int w, int h2, int w2, int C) {
-  SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "%s: bad dtype %d", what, dtype);
-  SEG_REQUIRE(C >= 8 && C % 8 == 0 && C <= MEU_MAX_C,
-              "%s: C=%d is not a positive multiple of 8 up to %d", what, C, MEU_MAX_C);
-  SEG_REQUIRE(N >= 1 && N <= 65535 && h >= 1 && w >= 1 && h2 >= 1 && w2 >= 1 && h2 <= h && w2 <= w &&
+// the `nld` pitches hold n channels in whole 4-channel vectors; rows -> chunks
+static int fpe_geometry(const char* what, int dtype, int N, int H, int W, int n, int dil, int rows,
+                        const long* lds, int nld, int* chunks) {
+  SEG_REQUIRE(H >= 1 && W >= 1 && (long)H * W < (1L << 31), "%s: bad shape H=%d W=%d", what, H, W);
+  SEG_REQUIRE(n <= FPE_MAX_N, "%s: n=%d is not a positive multiple of 4 up to %d", what, n,
+              FPE_MAX_N);
+  SEG_REQUIRE(dil >= 1 && dil <= FPE_MAX_DIL, "%s: dilation %d not in 1..%d", what, dil,
+              FPE_MAX_DIL);
+  if (fpe_rows_ok(what, rows, N, chunks)) return 1;
+  return rows_require(what, dtype, N, (long)H * W, n, FPE_V, FPE_V, lds, nullptr, nld, *chunks,
+                      CGN_MAX_CHUNKS);
+}
+
+// C a multiple of 8 (the low kernels' lane groups), pitches in whole 4-channel vectors
+static int meu_geometry(const char* what, int dtype, int N, int h, int w, int h2, int w2, int C,
+                        const long* lds, int nld, int chunks) {
+  SEG_REQUIRE(C <= MEU_MAX_C, "%s: C=%d is not a positive multiple of 8 up to %d", what, C,
+              MEU_MAX_C);
+  SEG_REQUIRE(h >= 1 && w >= 1 && h2 >= 1 && w2 >= 1 && h2 <= h && w2 <= w &&
                   (long)h * w < (1L << 31),
-              "%s: bad shape N=%d low %dx%d high %dx%d (1 <= high <= low)", what, N, h, w, h2, w2);
-  return 0;
+              "%s: bad shape low %dx%d high %dx%d (1 <= high <= low)", what, h, w, h2, w2);
+  return rows_require(what, dtype, N, (long)h * w, C, 8, FPE_V, lds, nullptr, nld, chunks,
+                      CGN_MAX_CHUNKS);
 }
 
 static void meu_fill(MeuArgs* a, int N, int h, int w, int h2, int w2, int C) {
@@ -515,21 +508,6 @@ static void meu_fill(MeuArgs* a, int N, int h, int w, int h2, int w2, int C) {
 
 }  // namespace seg
 
-#define FPE_TYPED(kernel, grid, block, a, stream)                                          \
-  do {                                                                                     \
-    if (dtype == DT_BF16)                                                                  \
-      hipLaunchKernelGGL((kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, a);        \
-    else                                                                                   \
-      hipLaunchKernelGGL((kernel<float>), grid, block, 0, (hipStream_t)stream, a);         \
-  } while (0)
-#define FPE_TYPED1(kernel, X, grid, block, a, stream)                                      \
-  do {                                                                                     \
-    if (dtype == DT_BF16)                                                                  \
-      hipLaunchKernelGGL((kernel<bf16_t, X>), grid, block, 0, (hipStream_t)stream, a);     \
-    else                                                                                   \
-      hipLaunchKernelGGL((kernel<float, X>), grid, block, 0, (hipStream_t)stream, a);      \
-  } while (0)
-
 // rows of the partial arrays of seg_fpe_stage_fwd / _bwd: chunks * N (-1: out of contract)
 extern "C" int seg_fpe_stage_rows(int dtype, int N, int H, int W, int n) {
   using namespace seg;
@@ -537,7 +515,7 @@ extern "C" int seg_fpe_stage_rows(int dtype, int N, int H, int W, int n) {
       n % 4 != 0 || n > FPE_MAX_N)
     return -1;
   const int CV = n / FPE_V;
-  return fpe_chunks(N, (long)H * W, CV, cgn_pick_cvb_log2(CV)) * N;
+  return fpe_chunks(N, (long)H * W, CV, rows_pick_cvb_log2(CV, 0)) * N;
 }
 
 extern "C" int seg_fpe_stage_fwd(int dtype, const void* a_, long lda, const float* sa,
@@ -546,27 +524,24 @@ extern "C" int seg_fpe_stage_fwd(int dtype, const void* a_, long lda, const floa
                                  void* b_act, long ldo, int N, int H, int W, int n, float* partial,
                                  int rows, void* stream) {
   using namespace seg;
-  if (fpe_geometry("fpe_stage_fwd", dtype, N, H, W, n, dil)) return 1;
   int chunks;
-  if (fpe_rows_ok("fpe_stage_fwd", rows, N, &chunks)) return 1;
+  // (a's pitch stands in for an absent operand's)
+  const long lds[4] = {lda, ldy, b != nullptr ? ldb : lda, b_act != nullptr ? ldo : lda};
+  if (fpe_geometry("fpe_stage_fwd", dtype, N, H, W, n, dil, rows, lds, 4, &chunks)) return 1;
   SEG_REQUIRE(a_ != nullptr && sa != nullptr && ta != nullptr && w != nullptr && y != nullptr,
               "fpe_stage_fwd: null a / sa / ta / w / y");
-  SEG_REQUIRE(lda % 4 == 0 && lda >= n && ldy % 4 == 0 && ldy >= n,
-              "fpe_stage_fwd: pitches %ld / %ld not multiples of 4 or below n", lda, ldy);
-  SEG_REQUIRE(b == nullptr ? b_act == nullptr
-                           : (sb != nullptr && tb != nullptr && ldb % 4 == 0 && ldb >= n),
-              "fpe_stage_fwd: b needs sb / tb and a pitch that is a multiple of 4 (b_act needs b)");
-  SEG_REQUIRE(b_act == nullptr || (ldo % 4 == 0 && ldo >= n), "fpe_stage_fwd: b_act pitch %ld", ldo);
+  SEG_REQUIRE(b == nullptr ? b_act == nullptr : (sb != nullptr && tb != nullptr),
+              "fpe_stage_fwd: b needs sb / tb (b_act needs b)");
   FpeFwdArgs a = FpeFwdArgs();
   a.a = a_; a.lda = lda; a.sa = sa; a.ta = ta; a.b = b; a.ldb = ldb; a.sb = sb; a.tb = tb;
   a.w = w; a.dil = dil; a.y = y; a.ldy = ldy; a.b_act = b_act; a.ldo = ldo; a.partial = partial;
-  a.N = N; a.H = H; a.W = W; a.n = n; a.CV = n / FPE_V; a.cvb_log2 = cgn_pick_cvb_log2(a.CV);
-  a.per = cgn_per((long)H * W, chunks, a.cvb_log2);
-  const dim3 grid = cgn_grid(a.CV, a.cvb_log2, chunks, N);
+  a.N = N; a.H = H; a.W = W; a.n = n; a.CV = n / FPE_V; a.cvb_log2 = rows_pick_cvb_log2(a.CV, 0);
+  a.per = rows_per((long)H * W, chunks, a.cvb_log2);
+  const dim3 grid = rows_grid(a.CV, a.cvb_log2, chunks, N);
   if (b != nullptr)
-    FPE_TYPED1(fpe_stage_fwd_kernel, true, grid, dim3(CGN_THREADS), a, stream);
+    SEG_LAUNCH_T((fpe_stage_fwd_kernel, true), grid, dim3(CGN_THREADS), 0, stream, a);
   else
-    FPE_TYPED1(fpe_stage_fwd_kernel, false, grid, dim3(CGN_THREADS), a, stream);
+    SEG_LAUNCH_T((fpe_stage_fwd_kernel, false), grid, dim3(CGN_THREADS), 0, stream, a);
   return check_launch("fpe_stage_fwd");
 }
 
@@ -589,9 +564,9 @@ static int fpe_flat(const char* what, bool bwd, int dtype, const void* g, long l
   SEG_REQUIRE((a.total + 255) / 256 < (1L << 31), "%s: too large", what);
   const dim3 grid((unsigned)((a.total + 255) / 256));
   if (bwd)
-    FPE_TYPED1(fpe_flat_kernel, true, grid, dim3(256), a, stream);
+    SEG_LAUNCH_T((fpe_flat_kernel, true), grid, dim3(256), 0, stream, a);
   else
-    FPE_TYPED1(fpe_flat_kernel, false, grid, dim3(256), a, stream);
+    SEG_LAUNCH_T((fpe_flat_kernel, false), grid, dim3(256), 0, stream, a);
   return check_launch(what);
 }
 
@@ -615,42 +590,37 @@ extern "C" int seg_fpe_stage_bwd(int dtype, const void* dy, long lddy, const voi
                                  int N, int H, int W, int n, float* pw, float* pa, long pa_pitch,
                                  int pa_col, float* pb, int rows, void* stream) {
   using namespace seg;
-  if (fpe_geometry("fpe_stage_bwd", dtype, N, H, W, n, dil)) return 1;
-  int chunks;
-  if (fpe_rows_ok("fpe_stage_bwd", rows, N, &chunks)) return 1;
   const bool tail = dy == nullptr, has_b = b != nullptr;
   SEG_REQUIRE(!tail || has_b, "fpe_stage_bwd: neither dy nor b");
+  int chunks;
+  const long any = tail ? ldb : lda;  // (a present operand's pitch stands in for an absent one's)
+  const long lds[6] = {tail ? any : lddy, tail ? any : lda, tail ? any : ldga,
+                       has_b ? ldb : any, has_b ? ldres : any, has_b ? ldgb : any};
+  if (fpe_geometry("fpe_stage_bwd", dtype, N, H, W, n, dil, rows, lds, 6, &chunks)) return 1;
   if (!tail) {
     SEG_REQUIRE(a_ != nullptr && sa != nullptr && ta != nullptr && w != nullptr && ga != nullptr &&
                     pw != nullptr && pa != nullptr,
                 "fpe_stage_bwd: null a / sa / ta / w / ga / pw / pa");
-    SEG_REQUIRE(lddy % 4 == 0 && lddy >= n && lda % 4 == 0 && lda >= n && ldga % 4 == 0 && ldga >= n,
-                "fpe_stage_bwd: a pitch of dy / a / ga is not a multiple of 4 or below n");
     SEG_REQUIRE(pa_col >= 0 && pa_col % 4 == 0 && pa_pitch >= (long)pa_col + n,
                 "fpe_stage_bwd: partial_a column %d + %d beyond its pitch %ld", pa_col, n, pa_pitch);
   }
   SEG_REQUIRE(has_b == (res != nullptr) && has_b == (gb != nullptr) && has_b == (pb != nullptr),
               "fpe_stage_bwd: b, res, gb and partial_b are null together");
-  if (has_b) {
-    SEG_REQUIRE(sb != nullptr && tb != nullptr, "fpe_stage_bwd: b needs sb / tb");
-    SEG_REQUIRE(ldb % 4 == 0 && ldb >= n && ldres % 4 == 0 && ldres >= n && ldgb % 4 == 0 &&
-                    ldgb >= n,
-                "fpe_stage_bwd: a pitch of b / res / gb is not a multiple of 4 or below n");
-  }
+  SEG_REQUIRE(!has_b || (sb != nullptr && tb != nullptr), "fpe_stage_bwd: b needs sb / tb");
   FpeBwdArgs a = FpeBwdArgs();
   a.dy = dy; a.lddy = lddy; a.a = a_; a.lda = lda; a.sa = sa; a.ta = ta;
   a.b = b; a.ldb = ldb; a.sb = sb; a.tb = tb; a.res = res; a.ldres = ldres; a.w = w; a.dil = dil;
   a.ga = ga; a.ldga = ldga; a.gb = gb; a.ldgb = ldgb; a.pw = pw; a.pa = pa; a.pa_pitch = pa_pitch;
   a.pa_col = pa_col; a.pb = pb;
-  a.N = N; a.H = H; a.W = W; a.n = n; a.CV = n / FPE_V; a.cvb_log2 = cgn_pick_cvb_log2(a.CV);
-  a.per = cgn_per((long)H * W, chunks, a.cvb_log2);
-  const dim3 grid = cgn_grid(a.CV, a.cvb_log2, chunks, N);
+  a.N = N; a.H = H; a.W = W; a.n = n; a.CV = n / FPE_V; a.cvb_log2 = rows_pick_cvb_log2(a.CV, 0);
+  a.per = rows_per((long)H * W, chunks, a.cvb_log2);
+  const dim3 grid = rows_grid(a.CV, a.cvb_log2, chunks, N);
   if (tail)
-    FPE_TYPED1(fpe_stage_bwd_kernel, 2, grid, dim3(CGN_THREADS), a, stream);
+    SEG_LAUNCH_T((fpe_stage_bwd_kernel, 2), grid, dim3(CGN_THREADS), 0, stream, a);
   else if (has_b)
-    FPE_TYPED1(fpe_stage_bwd_kernel, 1, grid, dim3(CGN_THREADS), a, stream);
+    SEG_LAUNCH_T((fpe_stage_bwd_kernel, 1), grid, dim3(CGN_THREADS), 0, stream, a);
   else
-    FPE_TYPED1(fpe_stage_bwd_kernel, 0, grid, dim3(CGN_THREADS), a, stream);
+    SEG_LAUNCH_T((fpe_stage_bwd_kernel, 0), grid, dim3(CGN_THREADS), 0, stream, a);
   return check_launch("fpe_stage_bwd");
 }
 
@@ -660,7 +630,7 @@ extern "C" int seg_meu_rows(int N, int h, int w, int C, int high) {
   using namespace seg;
   if (N < 1 || N > 65535 || h < 1 || w < 1 || C < 8 || C % 8 != 0 || C > MEU_MAX_C) return -1;
   const int CV = C / FPE_V;
-  const int l = high ? cgn_pick_cvb_log2(CV) : meu_lanes_log2(CV);
+  const int l = high ? rows_pick_cvb_log2(CV, 0) : rows_fit_cvb_log2(CV, 30);
   // (the low kernels keep a pixel's channels in one block row: one block column)
   return fpe_chunks(N, (long)h * w, high ? CV : 1 << l, l) * N;
 }
@@ -670,22 +640,21 @@ extern "C" int seg_meu_fwd(int dtype, const void* L, long ldl, const float* sl, 
                            const float* a_, const float* wsa, void* out, long ldo, float* sa, int N,
                            int h, int w, int h2, int w2, int C, void* stream) {
   using namespace seg;
-  if (meu_geometry("meu_fwd", dtype, N, h, w, h2, w2, C)) return 1;
+  const long lds[3] = {ldl, ldh, ldo};
+  if (meu_geometry("meu_fwd", dtype, N, h, w, h2, w2, C, lds, 3, 1)) return 1;
   SEG_REQUIRE(L != nullptr && Hr != nullptr && a_ != nullptr && wsa != nullptr && out != nullptr &&
                   sa != nullptr,
               "meu_fwd: null L / H / a / w_sa / out / sa");
   SEG_REQUIRE((sl == nullptr) == (tl == nullptr) && (sh == nullptr) == (th == nullptr),
               "meu_fwd: scale and shift go together");
-  SEG_REQUIRE(ldl % 4 == 0 && ldl >= C && ldh % 4 == 0 && ldh >= C && ldo % 4 == 0 && ldo >= C,
-              "meu_fwd: a pitch is not a multiple of 4 or below C");
   MeuArgs a = MeuArgs();
   meu_fill(&a, N, h, w, h2, w2, C);
   a.L = L; a.ldl = ldl; a.sl = sl; a.tl = tl; a.Hr = Hr; a.ldh = ldh; a.sh = sh; a.th = th;
   a.a = a_; a.wsa = wsa; a.out = out; a.ldo = ldo; a.sa = sa;
-  a.cvb_log2 = meu_lanes_log2(a.CV);
+  a.cvb_log2 = rows_fit_cvb_log2(a.CV, 30);
   const int chunks = fpe_chunks(N, (long)h * w, 1 << a.cvb_log2, a.cvb_log2);
-  a.per = cgn_per((long)h * w, chunks, a.cvb_log2);
-  FPE_TYPED1(meu_low_kernel, false, dim3(1, chunks, N), dim3(CGN_THREADS), a, stream);
+  a.per = rows_per((long)h * w, chunks, a.cvb_log2);
+  SEG_LAUNCH_T((meu_low_kernel, false), dim3(1, chunks, N), dim3(CGN_THREADS), 0, stream, a);
   return check_launch("meu_fwd");
 }
 
@@ -695,25 +664,23 @@ extern "C" int seg_meu_bwd_low(int dtype, const void* g, long ldg, const void* L
                                const float* sa, void* dL, long lddl, int N, int h, int w, int h2,
                                int w2, int C, float* p_a, float* p_bn, int rows, void* stream) {
   using namespace seg;
-  if (meu_geometry("meu_bwd_low", dtype, N, h, w, h2, w2, C)) return 1;
   int chunks;
+  const long lds[4] = {ldg, ldl, ldh, lddl};
   if (fpe_rows_ok("meu_bwd_low", rows, N, &chunks)) return 1;
+  if (meu_geometry("meu_bwd_low", dtype, N, h, w, h2, w2, C, lds, 4, chunks)) return 1;
   SEG_REQUIRE(g != nullptr && L != nullptr && Hr != nullptr && a_ != nullptr && wsa != nullptr &&
                   sa != nullptr && dL != nullptr && p_a != nullptr && p_bn != nullptr,
               "meu_bwd_low: null operand");
   SEG_REQUIRE((sl == nullptr) == (tl == nullptr) && (sh == nullptr) == (th == nullptr),
               "meu_bwd_low: scale and shift go together");
-  SEG_REQUIRE(ldg % 4 == 0 && ldg >= C && ldl % 4 == 0 && ldl >= C && ldh % 4 == 0 && ldh >= C &&
-                  lddl % 4 == 0 && lddl >= C,
-              "meu_bwd_low: a pitch is not a multiple of 4 or below C");
   MeuArgs a = MeuArgs();
   meu_fill(&a, N, h, w, h2, w2, C);
   a.g = g; a.ldg = ldg; a.L = L; a.ldl = ldl; a.sl = sl; a.tl = tl; a.Hr = Hr; a.ldh = ldh;
   a.sh = sh; a.th = th; a.a = a_; a.wsa = wsa; a.sa = const_cast<float*>(sa);
   a.out = dL; a.ldo = lddl; a.p1 = p_a; a.p2 = p_bn;
-  a.cvb_log2 = meu_lanes_log2(a.CV);
-  a.per = cgn_per((long)h * w, chunks, a.cvb_log2);
-  FPE_TYPED1(meu_low_kernel, true, dim3(1, chunks, N), dim3(CGN_THREADS), a, stream);
+  a.cvb_log2 = rows_fit_cvb_log2(a.CV, 30);
+  a.per = rows_per((long)h * w, chunks, a.cvb_log2);
+  SEG_LAUNCH_T((meu_low_kernel, true), dim3(1, chunks, N), dim3(CGN_THREADS), 0, stream, a);
   return check_launch("meu_bwd_low");
 }
 
@@ -721,20 +688,19 @@ extern "C" int seg_meu_bwd_high(int dtype, const void* g, long ldg, const float*
                                 long ldh, const float* dpool, void* dH, long lddh, int N, int h,
                                 int w, int h2, int w2, int C, float* p_bn, int rows, void* stream) {
   using namespace seg;
-  if (meu_geometry("meu_bwd_high", dtype, N, h, w, h2, w2, C)) return 1;
   int chunks;
+  const long lds[3] = {ldg, ldh, lddh};
   if (fpe_rows_ok("meu_bwd_high", rows, N, &chunks)) return 1;
+  if (meu_geometry("meu_bwd_high", dtype, N, h, w, h2, w2, C, lds, 3, chunks)) return 1;
   SEG_REQUIRE(g != nullptr && sa != nullptr && Hr != nullptr && dH != nullptr && p_bn != nullptr,
               "meu_bwd_high: null operand");
-  SEG_REQUIRE(ldg % 4 == 0 && ldg >= C && ldh % 4 == 0 && ldh >= C && lddh % 4 == 0 && lddh >= C,
-              "meu_bwd_high: a pitch is not a multiple of 4 or below C");
   MeuArgs a = MeuArgs();
   meu_fill(&a, N, h, w, h2, w2, C);
   a.g = g; a.ldg = ldg; a.sa = const_cast<float*>(sa); a.Hr = Hr; a.ldh = ldh; a.dpool = dpool;
   a.out = dH; a.ldo = lddh; a.p2 = p_bn;
-  a.cvb_log2 = cgn_pick_cvb_log2(a.CV);
-  a.per = cgn_per((long)h2 * w2, chunks, a.cvb_log2);
-  FPE_TYPED(meu_high_bwd_kernel, cgn_grid(a.CV, a.cvb_log2, chunks, N), dim3(CGN_THREADS), a,
-            stream);
+  a.cvb_log2 = rows_pick_cvb_log2(a.CV, 0);
+  a.per = rows_per((long)h2 * w2, chunks, a.cvb_log2);
+  SEG_LAUNCH_T(meu_high_bwd_kernel, rows_grid(a.CV, a.cvb_log2, chunks, N), dim3(CGN_THREADS), 0,
+               stream, a);
   return check_launch("meu_bwd_high");
 }

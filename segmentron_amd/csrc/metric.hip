@@ -10,12 +10,12 @@
 // lab[nclass]].  The fused variant takes the network's low-resolution NHWC logits and applies the
 // final bilinear upsample on the fly with exactly the arithmetic of seg_upsample_to_nchw
 // (resize.hip), so its arg-maxes are those of the materialised tensor.
-#include "common.h"
+#include "rows.h"
 #include "resize_taps.h"
 
 namespace seg {
 
-constexpr int MT_THREADS = 256;
+constexpr int MT_THREADS = 256, MT_MAX_BLOCKS = 2048;
 
 struct MetricAcc {
   int best_f, best_l;
@@ -113,11 +113,6 @@ __global__ __launch_bounds__(MT_THREADS) void metric_upsample_kernel(
   metric_flush(mt_cnt, ncnt, out);
 }
 
-static int metric_grid(long total) {
-  long g = (total + MT_THREADS - 1) / MT_THREADS;
-  return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-
 }  // namespace seg
 
 // logits: fp32 NCHW [N, C, H, W] (what SegBaseModel.evaluate returns); target int64 [N, H, W]
@@ -129,7 +124,8 @@ extern "C" int seg_metric_update_nchw(const float* logits, int N, int C, int H, 
               "metric_update_nchw: bad arguments");
   SEG_REQUIRE(nclass >= 1 && nclass <= 1024, "metric_update_nchw: nclass=%d", nclass);
   const long plane = (long)H * W;
-  hipLaunchKernelGGL(metric_nchw_kernel, dim3(metric_grid((long)N * plane)), dim3(MT_THREADS),
+  hipLaunchKernelGGL(metric_nchw_kernel,
+                     dim3(grid_1d((long)N * plane, MT_THREADS, MT_MAX_BLOCKS)), dim3(MT_THREADS),
                      (2 + 3 * nclass) * sizeof(unsigned), (hipStream_t)stream, logits, target, N, C,
                      plane, nclass, counters);
   return check_launch("metric_update_nchw");
@@ -150,7 +146,7 @@ extern "C" int seg_metric_update_upsample(int dtype, const void* lo, long ld, in
               "metric_update_upsample: ld=%ld must cover C=%d in whole %d-vectors", ld, C, vec);
   SEG_REQUIRE(nclass >= 1 && nclass <= 1024, "metric_update_upsample: nclass=%d", nclass);
   const float sh = host_scale(Hi, H, align_corners), sw = host_scale(Wi, W, align_corners);
-  const dim3 grid(metric_grid((long)N * H * W));
+  const dim3 grid(grid_1d((long)N * H * W, MT_THREADS, MT_MAX_BLOCKS));
   const size_t lds = (2 + 3 * nclass) * sizeof(unsigned);
   if (dtype == DT_BF16)
     hipLaunchKernelGGL((metric_upsample_kernel<bf16_t>), grid, dim3(MT_THREADS), lds,

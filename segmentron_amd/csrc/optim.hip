@@ -181,12 +181,7 @@ extern "C" int seg_pack_multi(int dtype, int njobs, const void* const* srcs, con
   int nj = 0, nb = 0;
   auto flush = [&]() -> int {
     if (nb == 0) { nj = 0; return 0; }
-    if (dtype == DT_BF16)
-      hipLaunchKernelGGL((pack_multi_kernel<bf16_t>), dim3(nb), dim3(PK_THREADS), 0,
-                         (hipStream_t)stream, a);
-    else
-      hipLaunchKernelGGL((pack_multi_kernel<float>), dim3(nb), dim3(PK_THREADS), 0,
-                         (hipStream_t)stream, a);
+    SEG_LAUNCH_T(pack_multi_kernel, dim3(nb), dim3(PK_THREADS), 0, stream, a);
     nj = nb = 0;
     return check_launch("pack_multi");
   };

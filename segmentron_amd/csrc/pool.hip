@@ -7,7 +7,7 @@
 // Adaptive average pooling uses ATen's bins [floor(i*H/o), ceil((i+1)*H/o)) (overlapping when
 // H % o != 0): forward emits fp32 partial sums per (bin, pixel chunk) that seg_colsum reduces;
 // backward gathers from the at most 2x2 bins that contain a pixel.
-#include "common.h"
+#include "rows.h"
 #include <float.h>
 
 namespace seg {
@@ -135,9 +135,9 @@ __global__ __launch_bounds__(PL_THREADS) void adaptive_avgpool_partial_kernel(co
   const int w0 = bin_start(bj, a.W, a.o), w1 = bin_end(bj, a.W, a.o);
   const int bw = w1 - w0, npix = (h1 - h0) * bw;
   const T* __restrict__ X = reinterpret_cast<const T*>(a.x);
-  float acc[VEC];
+  float acc[1][VEC];
 #pragma unroll
-  for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
+  for (int e = 0; e < VEC; ++e) acc[0][e] = 0.f;
   if (cv < a.CV) {
     const float inv_bw = 1.f / (float)bw;
     for (int q = blockIdx.y * spb + sy; q < npix; q += a.chunks * spb) {
@@ -146,19 +146,11 @@ __global__ __launch_bounds__(PL_THREADS) void adaptive_avgpool_partial_kernel(co
       float f[VEC];
       Vec<T>::unpack(ldg16(X + (((long)n * a.H + h) * a.W + w) * a.ldx + cv * VEC), f);
 #pragma unroll
-      for (int e = 0; e < VEC; ++e) acc[e] += f[e];
+      for (int e = 0; e < VEC; ++e) acc[0][e] += f[e];
     }
   }
-  float* mine = pl_smem + ((long)sy * cvb + cx) * VEC;
-#pragma unroll
-  for (int e = 0; e < VEC; ++e) mine[e] = acc[e];
-  __syncthreads();
-  for (int e = tid; e < cvb * VEC; e += PL_THREADS) {
-    float tot = 0.f;
-    for (int r = 0; r < spb; ++r) tot += pl_smem[(long)r * cvb * VEC + e];
-    const int c = blockIdx.x * cvb * VEC + e;
-    if (c < a.C) a.partial[((long)blockIdx.y * gridDim.z + bin) * a.C + c] = tot;
-  }
+  rows_block_reduce<VEC, 1, PL_THREADS>(pl_smem, acc, a.cvb_log2, blockIdx.x, a.C,
+                                        a.partial + ((long)blockIdx.y * gridDim.z + bin) * a.C, 0);
 }
 
 // gx[n,h,w,:] = sum_{bins containing (h,w)} gy[n,bi,bj,:] / area(bi,bj)
@@ -196,23 +188,7 @@ __global__ __launch_bounds__(PL_THREADS) void adaptive_avgpool_bwd_kernel(const 
   }
 }
 
-static int pl_grid(long total) {
-  long g = (total + PL_THREADS - 1) / PL_THREADS;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-static int pl_pick_cvb_log2(int CV) {
-  int best = 5;
-  double bu = 0;
-  for (int l = 5; l >= 3; --l) {
-    const int b = 1 << l;
-    const double u = (double)CV / (double)(((CV + b - 1) / b) * b);
-    if (u > bu + 1e-9) { bu = u; best = l; }
-  }
-  return best;
-}
+constexpr int PL_MAX_BLOCKS = 8192;  // grid-stride beyond
 
 }  // namespace seg
 
@@ -232,11 +208,8 @@ extern "C" int seg_maxpool_fwd(int dtype, const void* x, long ldx, int N, int Hi
   a.x = x; a.y = y; a.idx = (unsigned char*)idx; a.scale = pro_scale; a.shift = pro_shift;
   a.ldx = ldx; a.ldy = ldy; a.N = N; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.C = C;
   a.CV = C / vec; a.k = k; a.stride = stride; a.pad = pad; a.mode = pro_mode;
-  const int grid = pl_grid((long)N * Ho * Wo * a.CV);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((maxpool_fwd_kernel<bf16_t>), dim3(grid), dim3(PL_THREADS), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((maxpool_fwd_kernel<float>), dim3(grid), dim3(PL_THREADS), 0, (hipStream_t)stream, a);
+  const int grid = grid_1d((long)N * Ho * Wo * a.CV, PL_THREADS, PL_MAX_BLOCKS);
+  SEG_LAUNCH_T(maxpool_fwd_kernel, dim3(grid), dim3(PL_THREADS), 0, stream, a);
   return check_launch("maxpool_fwd");
 }
 
@@ -254,11 +227,8 @@ extern "C" int seg_maxpool_bwd(int dtype, void* gx, long ldgx, int N, int Hi, in
   a.scale = nullptr; a.shift = nullptr; a.ldx = ldgx; a.ldy = ldgy;
   a.N = N; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.C = C; a.CV = C / vec;
   a.k = k; a.stride = stride; a.pad = pad; a.mode = 0;
-  const int grid = pl_grid((long)N * Hi * Wi * a.CV);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t>), dim3(grid), dim3(PL_THREADS), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((maxpool_bwd_kernel<float>), dim3(grid), dim3(PL_THREADS), 0, (hipStream_t)stream, a);
+  const int grid = grid_1d((long)N * Hi * Wi * a.CV, PL_THREADS, PL_MAX_BLOCKS);
+  SEG_LAUNCH_T(maxpool_bwd_kernel, dim3(grid), dim3(PL_THREADS), 0, stream, a);
   return check_launch("maxpool_bwd");
 }
 
@@ -285,14 +255,10 @@ extern "C" int seg_adaptive_avgpool_partial(int dtype, const void* x, long ldx, 
   AvgPoolArgs a;
   a.x = x; a.gx = nullptr; a.gy = nullptr; a.partial = partial; a.ldx = ldx; a.ldg = 0; a.ldgy = 0;
   a.N = N; a.H = H; a.W = W; a.C = C; a.CV = C / vec; a.o = o; a.chunks = chunks;
-  a.cvb_log2 = pl_pick_cvb_log2(a.CV);
-  const int gx = (a.CV + (1 << a.cvb_log2) - 1) >> a.cvb_log2;
-  const dim3 grid(gx, chunks, N * o * o);
+  a.cvb_log2 = rows_pick_cvb_log2(a.CV, 3);
+  const dim3 grid(rows_gx(a.CV, a.cvb_log2), chunks, N * o * o);
   const size_t lds = (size_t)PL_THREADS * vec * sizeof(float);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((adaptive_avgpool_partial_kernel<bf16_t>), grid, dim3(PL_THREADS), lds, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((adaptive_avgpool_partial_kernel<float>), grid, dim3(PL_THREADS), lds, (hipStream_t)stream, a);
+  SEG_LAUNCH_T(adaptive_avgpool_partial_kernel, grid, dim3(PL_THREADS), lds, stream, a);
   return check_launch("adaptive_avgpool_partial");
 }
 
@@ -306,10 +272,7 @@ extern "C" int seg_adaptive_avgpool_bwd(int dtype, void* gx, long ldgx, int N, i
   AvgPoolArgs a;
   a.x = nullptr; a.gx = gx; a.gy = gy; a.partial = nullptr; a.ldx = 0; a.ldg = ldgx; a.ldgy = ldgy;
   a.N = N; a.H = H; a.W = W; a.C = C; a.CV = C / vec; a.o = o; a.chunks = 1; a.cvb_log2 = 0;
-  const int grid = pl_grid((long)N * H * W * a.CV);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((adaptive_avgpool_bwd_kernel<bf16_t>), dim3(grid), dim3(PL_THREADS), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((adaptive_avgpool_bwd_kernel<float>), dim3(grid), dim3(PL_THREADS), 0, (hipStream_t)stream, a);
+  const int grid = grid_1d((long)N * H * W * a.CV, PL_THREADS, PL_MAX_BLOCKS);
+  SEG_LAUNCH_T(adaptive_avgpool_bwd_kernel, dim3(grid), dim3(PL_THREADS), 0, stream, a);
   return check_launch("adaptive_avgpool_bwd");
 }

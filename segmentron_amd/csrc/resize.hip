@@ -10,12 +10,13 @@
 // whose (i0, i1, lambda) are re-derived — once per block, as lists of the rows and columns that
 // carry weight.  Forward and backward blocks own one row of pixels (block-uniform row taps, no
 // division per element); the forward applies the pending BatchNorm / ReLU once per source vector.
-#include "common.h"
+#include "rows.h"
 #include "resize_taps.h"
 
 namespace seg {
 
 constexpr int RS_THREADS = 256;
+constexpr int RS_MAX_BLOCKS = 8192;  // of the grid-stride kernels
 
 struct ResizeArgs {
   const void* x; void* y;
@@ -488,13 +489,6 @@ __global__ __launch_bounds__(RS_THREADS) void nearest_sum_bwd_kernel(const AddUp
   }
 }
 
-static int rs_grid(long total) {
-  long g = (total + RS_THREADS - 1) / RS_THREADS;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 static int fill_args(ResizeArgs& a, int dtype, const void* x, long ldx, int N, int Hi, int Wi,
                      int C, void* y, long ldy, int Ho, int Wo, int align, bool need_vec_c) {
   const int vec = dtype == DT_BF16 ? 8 : 4;
@@ -546,12 +540,8 @@ extern "C" int seg_bilinear_fwd(int dtype, const void* x, long ldx, int N, int H
   ns_cap = ns_max;
   const size_t lds = (size_t)2 * ns_cap * vec * cvb * sizeof(float);
   const dim3 grid(nseg * ncb, Ho, N);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((bilinear_fwd_kernel<bf16_t>), grid, dim3(RS_THREADS), lds,
-                       (hipStream_t)stream, a, segw, nseg, ns_cap, cvb);
-  else
-    hipLaunchKernelGGL((bilinear_fwd_kernel<float>), grid, dim3(RS_THREADS), lds,
-                       (hipStream_t)stream, a, segw, nseg, ns_cap, cvb);
+  SEG_LAUNCH_T(bilinear_fwd_kernel, grid, dim3(RS_THREADS), lds, stream, a, segw, nseg, ns_cap,
+               cvb);
   return check_launch("bilinear_fwd");
 }
 
@@ -568,12 +558,7 @@ extern "C" int seg_bilinear_bwd(int dtype, void* gx, long ldgx, int N, int Hi, i
   if ((long)Ho * Wo >= 64L * Hi * Wi) {
     const long nblk = (long)N * Hi * Wi * ((a.CV + RSW_CVB - 1) / RSW_CVB);
     SEG_REQUIRE(nblk < (1L << 31), "bilinear_bwd: too many blocks");
-    if (dtype == DT_BF16)
-      hipLaunchKernelGGL((bilinear_bwd_wide_kernel<bf16_t>), dim3((unsigned)nblk),
-                         dim3(RS_THREADS), 0, (hipStream_t)stream, a);
-    else
-      hipLaunchKernelGGL((bilinear_bwd_wide_kernel<float>), dim3((unsigned)nblk), dim3(RS_THREADS),
-                         0, (hipStream_t)stream, a);
+    SEG_LAUNCH_T(bilinear_bwd_wide_kernel, dim3((unsigned)nblk), dim3(RS_THREADS), 0, stream, a);
     return check_launch("bilinear_bwd (wide)");
   }
   SEG_REQUIRE(N <= 65535 && Hi <= 65535, "bilinear_bwd: N=%d / Hi=%d beyond the launch grid", N, Hi);
@@ -591,12 +576,8 @@ extern "C" int seg_bilinear_bwd(int dtype, void* gx, long ldgx, int N, int Hi, i
   if (nsc > Wi) nsc = Wi;
   const int nsegs = (Wi + nsc - 1) / nsc;
   const dim3 grid(nsegs * ncb, Hi, N);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((bilinear_bwd_kernel<bf16_t>), grid, dim3(RS_THREADS), 0,
-                       (hipStream_t)stream, a, nsc, nsegs, kc, cvb, use_tab);
-  else
-    hipLaunchKernelGGL((bilinear_bwd_kernel<float>), grid, dim3(RS_THREADS), 0,
-                       (hipStream_t)stream, a, nsc, nsegs, kc, cvb, use_tab);
+  SEG_LAUNCH_T(bilinear_bwd_kernel, grid, dim3(RS_THREADS), 0, stream, a, nsc, nsegs, kc, cvb,
+               use_tab);
   return check_launch("bilinear_bwd");
 }
 
@@ -609,22 +590,12 @@ extern "C" int seg_upsample_to_nchw(int dtype, const void* x, long ldx, int N, i
   if (fill_args(a, dtype, x, ldx, N, Hi, Wi, C, nullptr, 0, Ho, Wo, align_corners, false)) return 1;
   SEG_REQUIRE(ldx >= (long)a.CV * (dtype == DT_BF16 ? 8 : 4), "upsample_to_nchw: ldx too small");
   if (Wo % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
-    const int grid4 = rs_grid((long)N * Ho * (Wo / 4));
-    if (dtype == DT_BF16)
-      hipLaunchKernelGGL((upsample_to_nchw_v4_kernel<bf16_t>), dim3(grid4), dim3(RS_THREADS), 0,
-                         (hipStream_t)stream, a, out);
-    else
-      hipLaunchKernelGGL((upsample_to_nchw_v4_kernel<float>), dim3(grid4), dim3(RS_THREADS), 0,
-                         (hipStream_t)stream, a, out);
+    const int grid4 = grid_1d((long)N * Ho * (Wo / 4), RS_THREADS, RS_MAX_BLOCKS);
+    SEG_LAUNCH_T(upsample_to_nchw_v4_kernel, dim3(grid4), dim3(RS_THREADS), 0, stream, a, out);
     return check_launch("upsample_to_nchw");
   }
-  const int grid = rs_grid((long)N * Ho * Wo);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((upsample_to_nchw_kernel<bf16_t>), dim3(grid), dim3(RS_THREADS), 0,
-                       (hipStream_t)stream, a, out);
-  else
-    hipLaunchKernelGGL((upsample_to_nchw_kernel<float>), dim3(grid), dim3(RS_THREADS), 0,
-                       (hipStream_t)stream, a, out);
+  const int grid = grid_1d((long)N * Ho * Wo, RS_THREADS, RS_MAX_BLOCKS);
+  SEG_LAUNCH_T(upsample_to_nchw_kernel, dim3(grid), dim3(RS_THREADS), 0, stream, a, out);
   return check_launch("upsample_to_nchw");
 }
 
@@ -637,13 +608,8 @@ extern "C" int seg_upsample_to_nchw_bwd(int dtype, void* gx, long ldgx, int N, i
     return 1;
   SEG_REQUIRE(ldgx >= (long)a.CV * (dtype == DT_BF16 ? 8 : 4), "upsample_to_nchw_bwd: ld small");
   a.CV = (int)(ldgx / (dtype == DT_BF16 ? 8 : 4));  // zero-fill every padded channel of gx
-  const int grid = rs_grid((long)N * Hi * Wi);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((upsample_to_nchw_bwd_kernel<bf16_t>), dim3(grid), dim3(RS_THREADS), 0,
-                       (hipStream_t)stream, a, gy);
-  else
-    hipLaunchKernelGGL((upsample_to_nchw_bwd_kernel<float>), dim3(grid), dim3(RS_THREADS), 0,
-                       (hipStream_t)stream, a, gy);
+  const int grid = grid_1d((long)N * Hi * Wi, RS_THREADS, RS_MAX_BLOCKS);
+  SEG_LAUNCH_T(upsample_to_nchw_bwd_kernel, dim3(grid), dim3(RS_THREADS), 0, stream, a, gy);
   return check_launch("upsample_to_nchw_bwd");
 }
 
@@ -654,7 +620,7 @@ extern "C" int seg_nchw_to_nhwc_pad(int dtype, const float* x, int N, int Cin, i
   SEG_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "nchw_to_nhwc_pad: bad dtype %d", dtype);
   SEG_REQUIRE(Cin >= 1 && Cin <= vec, "nchw_to_nhwc_pad: Cin=%d must be <= %d", Cin, vec);
   const long HW = (long)H * W;
-  const int grid = rs_grid((long)N * HW);
+  const int grid = grid_1d((long)N * HW, RS_THREADS, RS_MAX_BLOCKS);
   if (dtype == DT_BF16)
     hipLaunchKernelGGL((nchw_to_nhwc_pad_kernel<bf16_t>), dim3(grid), dim3(RS_THREADS), 0,
                        (hipStream_t)stream, x, reinterpret_cast<bf16_t*>(y), N, Cin, HW);
@@ -681,11 +647,8 @@ extern "C" int seg_nearest_add(int dtype, const void* x, long ldx, int mode_x, c
   a.x = x; a.r = r; a.y = y; a.sx = sx; a.tx = tx; a.sr = sr; a.tr = tr;
   a.ldx = ldx; a.ldr = ldr; a.ldy = ldy; a.N = N; a.H = H; a.W = W; a.C = C; a.CV = C / vec;
   a.mode_x = mode_x; a.mode_r = mode_r; a.shift = shift; a.post_relu = post_relu;
-  const int grid = rs_grid((long)N * H * W * a.CV);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((nearest_add_kernel<bf16_t>), dim3(grid), dim3(RS_THREADS), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((nearest_add_kernel<float>), dim3(grid), dim3(RS_THREADS), 0, (hipStream_t)stream, a);
+  const int grid = grid_1d((long)N * H * W * a.CV, RS_THREADS, RS_MAX_BLOCKS);
+  SEG_LAUNCH_T(nearest_add_kernel, dim3(grid), dim3(RS_THREADS), 0, stream, a);
   return check_launch("nearest_add");
 }
 
@@ -704,10 +667,7 @@ extern "C" int seg_nearest_sum_bwd(int dtype, const void* g, long ldg, int N, in
   a.x = g; a.r = nullptr; a.y = gr; a.sx = a.tx = a.sr = a.tr = nullptr;
   a.ldx = ldg; a.ldr = 0; a.ldy = ldgr; a.N = N; a.H = H; a.W = W; a.C = C; a.CV = C / vec;
   a.mode_x = 0; a.mode_r = 0; a.shift = shift; a.post_relu = 0;
-  const int grid = rs_grid((long)N * (H >> shift) * (W >> shift) * a.CV);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((nearest_sum_bwd_kernel<bf16_t>), dim3(grid), dim3(RS_THREADS), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((nearest_sum_bwd_kernel<float>), dim3(grid), dim3(RS_THREADS), 0, (hipStream_t)stream, a);
+  const int grid = grid_1d((long)N * (H >> shift) * (W >> shift) * a.CV, RS_THREADS, RS_MAX_BLOCKS);
+  SEG_LAUNCH_T(nearest_sum_bwd_kernel, dim3(grid), dim3(RS_THREADS), 0, stream, a);
   return check_launch("nearest_sum_bwd");
 }

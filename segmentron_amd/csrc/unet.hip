@@ -17,7 +17,7 @@
 //       blend expression as resize.hip.  Only the levels with an odd size come here.
 //
 // All four are memory-bound: one 16-byte vector along C per lane and access.
-#include "common.h"
+#include "rows.h"
 #include "resize_taps.h"
 
 namespace seg {
@@ -114,7 +114,7 @@ template <typename T>
 __global__ __launch_bounds__(UN_THREADS) void skip_pool_bwd_kernel(const SkipPoolArgs a,
                                                                    int cvb_log2) {
   constexpr int VEC = Vec<T>::N;
-  __shared__ float red[UN_THREADS][2 * VEC];
+  __shared__ float red[2 * UN_THREADS * VEC];
   const T* __restrict__ Y = reinterpret_cast<const T*>(a.y);
   const T* __restrict__ GS = reinterpret_cast<const T*>(a.gs);
   const T* __restrict__ GP = reinterpret_cast<const T*>(a.gp);
@@ -128,10 +128,10 @@ __global__ __launch_bounds__(UN_THREADS) void skip_pool_bwd_kernel(const SkipPoo
   const int Hp = a.H >> 1, Wp = a.W >> 1;
   const int nwin = a.N * a.Hw * a.Ww;
   const float inv_ww = 1.f / (float)a.Ww, inv_hw = 1.f / (float)a.Hw;
-  float s[VEC], t[VEC], ag[VEC], agy[VEC];
+  float s[VEC], t[VEC], acc[2][VEC];  // sum g, sum g * y
   un_params<VEC>(a, c0, s, t);
 #pragma unroll
-  for (int e = 0; e < VEC; ++e) { ag[e] = 0.f; agy[e] = 0.f; }
+  for (int e = 0; e < VEC; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
   if (cok) {
     for (int w = blockIdx.x * npl + pl; w < nwin; w += gridDim.x * npl) {
       int q = fast_div(w, a.Ww, inv_ww);
@@ -182,25 +182,16 @@ __global__ __launch_bounds__(UN_THREADS) void skip_pool_bwd_kernel(const SkipPoo
         for (int e = 0; e < VEC; ++e) {
           if (full && bi[e] == k) g[e] += gp[e];
           if ((a.mode & PRO_RELU) && !(r[k][e] > 0.f)) g[e] = 0.f;
-          ag[e] += g[e];
-          agy[e] += g[e] * yf[e];
+          acc[0][e] += g[e];
+          acc[1][e] += g[e] * yf[e];
         }
         stg16(GX + off[k] * a.ldgx + c0, Vec<T>::pack(g));
       }
     }
   }
-#pragma unroll
-  for (int e = 0; e < VEC; ++e) { red[tid][e] = ag[e]; red[tid][VEC + e] = agy[e]; }
-  __syncthreads();
   // the window lanes' sums meet in lane order: [row][which][C]
-  for (int i = tid; i < 2 * cvb * VEC; i += UN_THREADS) {
-    const int which = i / (cvb * VEC), rem = i - which * cvb * VEC;
-    const int lx = rem / VEC, e = rem - lx * VEC;
-    float tot = 0.f;
-    for (int l = 0; l < npl; ++l) tot += red[(l << cvb_log2) + lx][which * VEC + e];
-    const int c = (blockIdx.y * cvb + lx) * VEC + e;
-    if (c < a.C) a.partial[((long)blockIdx.x * 2 + which) * a.C + c] = tot;
-  }
+  rows_block_reduce<VEC, 2, UN_THREADS>(red, acc, cvb_log2, blockIdx.y, a.C,
+                                        a.partial + (long)blockIdx.x * 2 * a.C, a.C);
 }
 
 // ---------------------------------------------------------------- bilinear with a destination window
@@ -308,19 +299,11 @@ __global__ __launch_bounds__(UN_THREADS) void bilinear_pad_bwd_kernel(const Plac
   }
 }
 
-static int un_grid(long total) {
-  long g = (total + UN_THREADS - 1) / UN_THREADS;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (int)g;
-}
+constexpr int UN_MAX_BLOCKS = 8192;  // grid-stride beyond
 
-// channel-vector lanes of a backward block: the smallest power of two that holds CV, 32 at the most
-static int un_cvb_log2(int CV) {
-  int l = 0;
-  while ((1 << l) < CV && l < 5) ++l;
-  return l;
-}
+// channel-vector lanes of a backward block: the smallest power of two that holds CV
+// (rows_fit_cvb_log2), 32 at the most; the rest of the block's threads are its window lanes
+constexpr int UN_MAX_LANES_LOG2 = 5;
 
 static int fill_skip_pool(SkipPoolArgs& a, const char* what, int dtype, int N, int H, int W, int C,
                           int pro_mode, const float* pro_scale, const float* pro_shift) {
@@ -355,13 +338,8 @@ extern "C" int seg_skip_pool_fwd(int dtype, const void* y, long ldy, int N, int 
                   ldpool % vec == 0, "skip_pool_fwd: pitches are multiples of %d, at least C", vec);
   SEG_REQUIRE_FAST_DIV("skip_pool_fwd", (long)N * a.Hw * a.Ww, a.CV);
   a.y = y; a.ldy = ldy; a.skip = skip; a.lds = ldskip; a.pooled = pooled; a.ldp = ldpool;
-  const int grid = un_grid((long)N * a.Hw * a.Ww * a.CV);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((skip_pool_fwd_kernel<bf16_t>), dim3(grid), dim3(UN_THREADS), 0,
-                       (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((skip_pool_fwd_kernel<float>), dim3(grid), dim3(UN_THREADS), 0,
-                       (hipStream_t)stream, a);
+  const int grid = grid_1d((long)N * a.Hw * a.Ww * a.CV, UN_THREADS, UN_MAX_BLOCKS);
+  SEG_LAUNCH_T(skip_pool_fwd_kernel, dim3(grid), dim3(UN_THREADS), 0, stream, a);
   return check_launch("skip_pool_fwd");
 }
 
@@ -371,7 +349,7 @@ extern "C" int seg_skip_pool_bwd_rows(int dtype, int N, int H, int W, int C) {
   if ((dtype != DT_F32 && dtype != DT_BF16) || N < 1 || H < 2 || W < 2 || C < 1) return 0;
   const int vec = dtype == DT_BF16 ? 8 : 4;
   if (C % vec != 0) return 0;
-  const int npl = UN_THREADS >> un_cvb_log2(C / vec);
+  const int npl = UN_THREADS >> rows_fit_cvb_log2(C / vec, UN_MAX_LANES_LOG2);
   const long nwin = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
   long r = (nwin + npl - 1) / npl;
   if (r > UN_MAX_ROWS) r = UN_MAX_ROWS;
@@ -396,15 +374,10 @@ extern "C" int seg_skip_pool_bwd(int dtype, const void* g_skip, long ldgs, const
   SEG_REQUIRE_FAST_DIV("skip_pool_bwd", (long)N * a.Hw, a.Ww);
   a.y = y; a.ldy = ldy; a.gs = g_skip; a.ldgs = ldgs; a.gp = g_pool; a.ldgp = ldgp;
   a.gx = gx; a.ldgx = ldgx; a.partial = partial;
-  const int l2 = un_cvb_log2(a.CV);
-  const dim3 grid(rows, (a.CV + (1 << l2) - 1) >> l2);
+  const int l2 = rows_fit_cvb_log2(a.CV, UN_MAX_LANES_LOG2);
+  const dim3 grid(rows, rows_gx(a.CV, l2));
   SEG_REQUIRE(grid.y <= 65535, "skip_pool_bwd: C = %d beyond the launch grid", C);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((skip_pool_bwd_kernel<bf16_t>), grid, dim3(UN_THREADS), 0,
-                       (hipStream_t)stream, a, l2);
-  else
-    hipLaunchKernelGGL((skip_pool_bwd_kernel<float>), grid, dim3(UN_THREADS), 0,
-                       (hipStream_t)stream, a, l2);
+  SEG_LAUNCH_T(skip_pool_bwd_kernel, grid, dim3(UN_THREADS), 0, stream, a, l2);
   return check_launch("skip_pool_bwd");
 }
 
@@ -444,13 +417,8 @@ extern "C" int seg_bilinear_pad_fwd(int dtype, const void* x, long ldx, int N, i
   SEG_REQUIRE_FAST_DIV("bilinear_pad_fwd", (long)N * Hd * Wd, a.CV);
   SEG_REQUIRE((long)N * Hd * Wd * a.CV < (1L << 30), "bilinear_pad_fwd: too many vectors");
   a.x = x; a.y = y; a.mode = pro_mode; a.scale = pro_scale; a.shift = pro_shift;
-  const int grid = un_grid((long)N * Hd * Wd * a.CV);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((bilinear_pad_fwd_kernel<bf16_t>), dim3(grid), dim3(UN_THREADS), 0,
-                       (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((bilinear_pad_fwd_kernel<float>), dim3(grid), dim3(UN_THREADS), 0,
-                       (hipStream_t)stream, a);
+  const int grid = grid_1d((long)N * Hd * Wd * a.CV, UN_THREADS, UN_MAX_BLOCKS);
+  SEG_LAUNCH_T(bilinear_pad_fwd_kernel, dim3(grid), dim3(UN_THREADS), 0, stream, a);
   return check_launch("bilinear_pad_fwd");
 }
 
@@ -467,12 +435,7 @@ extern "C" int seg_bilinear_pad_bwd(int dtype, void* gx, long ldgx, int N, int H
   SEG_REQUIRE_FAST_DIV("bilinear_pad_bwd", (long)N * Hi * Wi, a.CV);
   SEG_REQUIRE((long)N * Hi * Wi * a.CV < (1L << 30), "bilinear_pad_bwd: too many vectors");
   a.x = gx; a.y = const_cast<void*>(gy);
-  const int grid = un_grid((long)N * Hi * Wi * a.CV);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL((bilinear_pad_bwd_kernel<bf16_t>), dim3(grid), dim3(UN_THREADS), 0,
-                       (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL((bilinear_pad_bwd_kernel<float>), dim3(grid), dim3(UN_THREADS), 0,
-                       (hipStream_t)stream, a);
+  const int grid = grid_1d((long)N * Hi * Wi * a.CV, UN_THREADS, UN_MAX_BLOCKS);
+  SEG_LAUNCH_T(bilinear_pad_bwd_kernel, dim3(grid), dim3(UN_THREADS), 0, stream, a);
   return check_launch("bilinear_pad_bwd");
 }

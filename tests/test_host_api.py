@@ -361,6 +361,32 @@ def test_depthwise_grid_queries_equal_the_recorded_ones_and_refuse_bad_input(gol
         assert q("seg_dwconv3x3_s2_grid_y", *args) == -1
 
 
+def test_rows_geometry_queries_equal_the_recorded_ones(golden_dir):
+    """tests/golden/rows_queries.json (oracle/gen_golden_rows_queries.py) holds what the chunk,
+    partial-row and grid queries answered BEFORE their arithmetic moved into csrc/rows.h, recorded
+    from that commit's build over the sweep of tests/_rows_queries.py: N 1..3, maps from 1 x 1 to
+    513 x 1025, channel counts on every lane width of both pickers (idle lanes included), both
+    dtypes, and out-of-contract arguments.  Python sizes every partial buffer by these answers and
+    the kernels index by the same geometry: the library answers the same at every point."""
+    import _rows_queries
+    from segmentron_amd import _lib
+    rec = json.load(open(os.path.join(golden_dir, "rows_queries.json")))
+    want = rec["values"]
+    got = _rows_queries.sweep(_lib.LIB.query)
+    assert sorted(got) == sorted(want) and len(want) == 9
+    assert sum(len(v) for v in want.values()) == 10135
+    # the sweep reaches what it is for: refusals, one chunk and the caps
+    assert min(want["seg_cg_joint_chunks"]) == -1 and max(want["seg_cg_joint_chunks"]) == 256
+    assert max(want["seg_apply_pool_chunks"]) == 64 and 1 in want["seg_eesp_pyr_chunks"]
+    assert 0 in want["seg_skip_pool_bwd_rows"] and max(want["seg_skip_pool_bwd_rows"]) == 1024
+    calls = _rows_queries.calls()
+    for name in want:
+        args = [a for n, a in calls if n == name]
+        bad = [(a, g, w) for a, g, w in zip(args, got[name], want[name]) if g != w]
+        assert len(got[name]) == len(want[name]) and not bad, \
+            "%s: %d points differ, first %s -> %d, recorded %d" % ((name, len(bad)) + bad[0])
+
+
 FAST_DIV_DIVISORS = (1, 3, 5, 6, 7, 10, 16, 33, 91, 257, 1000)
 # smallest wrong dividends a random search of the float-reciprocal division found, per divisor
 FAST_DIV_KNOWN_WRONG = ((3, 33554942), (5, 67109429), (6, 67109596), (8, 268435605),
