@@ -547,6 +547,36 @@ int seg_bilinear_pad_bwd(int dtype, void* gx, long ldgx, int N, int Hi, int Wi, 
                          long ldgy, int Ho, int Wo, int Hd, int Wd, int top, int left,
                          int align_corners, void* stream);
 
+/* ---- ContextNet's fusion: bilinear resize + depthwise 3x3 without the upsampled map ------------
+ * (csrc/contextnet.hip; segmentron/models/contextnet.py:180-183)
+ * NHWC, fp32 and bf16, a channel pitch per operand, C a multiple of the 16-byte vector (4 / 8).
+ * No atomics: bit-identical results on every launch.  Any h, w, H, W >= 1 (h == 1 or w == 1: scale
+ * 0 on that axis).  U = F.interpolate(act(lo), (H, W), 'bilinear', align_corners) of lo [N,h,w,C],
+ * act = the seg_bilinear_fwd prologue (pro_mode / scale / shift) applied to each source tap before
+ * the blend; U is ZERO outside [0,H) x [0,W) (the padding belongs to the upsampled map), lives in
+ * registers and LDS in fp32 and is never rounded to the activation dtype.  w9c: fp32 [9][C]
+ * tap-major.
+ *   seg_up_dw_rows   partial rows of a launch (pure host; 0: bad arguments).  kind 0: the forward's
+ *                    statistics rows, kind 1: the backward's weight-gradient rows.  The launchers
+ *                    take exactly this many.
+ *   seg_up_dw_fwd    y[n,Y,X,c] = sum_{i,j in -1..1} w9c[(i+1)*3+(j+1)][c] * U[n,Y+i,X+j,c].
+ *                    stat_partial (nullable): [rows][2][C] = sum | sum of squares of the fp32
+ *                    outputs, what seg_dwconv3x3 hands to seg_bn_finalize_p.
+ *   seg_up_dw_bwd    one pass over dy [N,H,W,C] and lo: d_up [N,H,W,C] = the correlation of dy with
+ *                    the flipped taps, in the activation dtype (no mask: nothing stands between the
+ *                    resize and the convolution; seg_bilinear_bwd takes it next), and
+ *                    partial_w [rows][9][C] = sum dy[Y,X] * U[Y+i,X+j] with U recomputed from lo
+ *                    (reduce with seg_dwconv3x3_wgrad_finalize). */
+int seg_up_dw_rows(int dtype, int N, int H, int W, int C, int kind);
+int seg_up_dw_fwd(int dtype, const void* lo, long ldlo, int N, int h, int w, int C, int pro_mode,
+                  const float* pro_scale, const float* pro_shift, const float* w9c, void* y,
+                  long ldy, int H, int W, int align_corners, float* stat_partial, int rows,
+                  void* stream);
+int seg_up_dw_bwd(int dtype, const void* dy, long lddy, const void* lo, long ldlo, int N, int h,
+                  int w, int C, int pro_mode, const float* pro_scale, const float* pro_shift,
+                  const float* w9c, void* d_up, long ldd, int H, int W, int align_corners,
+                  float* partial_w, int rows, void* stream);
+
 /* ---- F.interpolate(mode='bilinear') ---------------------------------------------------------
  * Replaces segmentron/models/deeplabv3_plus.py:39,44,71; segmentron/modules/module.py:64,96;
  * segmentron/models/segbase.py:83.  NHWC -> NHWC with optional prologue and per-(n,c) multiplier. */

@@ -3158,3 +3158,101 @@ def bilinear_placed(act, out_hw, out, place=(0, 0), align_corners=True):
     g, b = act.params
     return _BilinearPadFn.apply(act.t, g, b, PlacedResizeSpec(act, out_hw, tuple(place),
                                                               align_corners, out))
+
+
+# ---- ContextNet: the fusion's resize + depthwise 3x3 as one node (csrc/contextnet.hip) -------------
+_CTX_UP_DW = os.environ.get("SEG_CTX_UP_DW")  # "0" / "1": force the two-launch route / the node
+# (dtype, C, output rows above hip_ops.SMALL_BN_ROWS) classes in which the node measured FASTER than
+# bilinear + dwconv_bn and their backward by more than the spread of the repeats, forward and
+# backward together, in the same run (tools/contextnet_bench.py, profiles/contextnet.md); every
+# other class keeps the existing route
+_UP_DW_WON = frozenset()
+
+
+def up_dw_routed(dtype, C, rows):
+    """Does functional.up_dwconv_bn run the fused node for a C-channel output of `rows` = N*H*W
+    pixels in `dtype`?"""
+    if _CTX_UP_DW in ("0", "1"):
+        return _CTX_UP_DW == "1"
+    return (dtype, int(C), rows > K.SMALL_BN_ROWS) in _UP_DW_WON
+
+
+class UpDwSpec:
+    def __init__(self, a, out_hw, align_corners, out, want_stats):
+        self.bn, self.relu, self.pro = a.bn, a.relu, a.pro
+        self.out_hw, self.align, self.out, self.want_stats = out_hw, align_corners, out, want_stats
+        self.partial = None
+
+
+class _UpDwFn(torch.autograd.Function):
+    """nn.Conv2d(groups=C, 3x3, padding=1) of F.interpolate(mode='bilinear') of a deferred
+    activation in ONE launch (csrc/contextnet.hip seg_up_dw_fwd): the upsampled map lives in
+    registers.  Only the low map and the weight are saved; seg_up_dw_bwd recomputes the upsampled
+    map for the weight gradient and writes the transient d_up, which then takes _BilinearFn's
+    backward: seg_bilinear_bwd (the per-image column sum for a 1 x 1 low map) and the BatchNorm
+    backward of the low map's pending prologue under its own launch policy."""
+
+    @staticmethod
+    def forward(ctx, x, in_gamma, in_beta, weight, spec):
+        w9c = cached_pack(weight, "dw", lambda: pack_dw_weight(weight))
+        y, spec.partial = K.up_dw(x, spec.out_hw, w9c, spec.pro, spec.align, spec.out,
+                                  spec.want_stats)
+        spec.out = None  # (it IS y: kept, ctx -> spec -> y -> grad_fn -> ctx would be a cycle)
+        ctx.spec = spec
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        s = ctx.spec
+        N, h, w, C = x.shape
+        dy = _grad_operand(dy, x.dtype, K.vec_of(x.dtype))
+        w9c = cached_pack(weight, "dw", lambda: pack_dw_weight(weight))
+        d_up, pw = K.up_dw_bwd(dy, x, w9c, s.pro, s.align)
+        dW = K.dw_wgrad_finalize(pw.view(pw.shape[0], 9 * C), C)
+        del pw
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, dW, None
+        if h == 1 and w == 1:
+            # every output pixel copies the single input pixel: gradient = per-image column sum
+            ga = torch.stack([K.bn_bwd_reduce(d_up[n:n + 1], d_up[n:n + 1],
+                                              (PRO_NONE, None, None))[:C]
+                              for n in range(N)]).to(x.dtype).view(N, 1, 1, C)
+        else:
+            ga = K.bilinear_bwd(d_up, (h, w), s.align)
+        del d_up
+        dx, dgamma, dbeta = bn_input_backward(ga, x, s.bn, s.relu, inplace=True)
+        return dx, dgamma, dbeta, dW, None
+
+
+def up_dwconv_bn(act_lo, out_hw, conv, bn, out=None, align_corners=True):
+    """bn(conv(F.interpolate(act(lo), out_hw, 'bilinear', align_corners))) for a bias-free depthwise
+    3x3 `conv` (stride 1, padding 1, dilation 1, weight [C,1,3,3]) -> Act(y, finish_bn(...)); the
+    caller sets ``.relu``.  One autograd node on csrc/contextnet.hip where up_dw_routed, else
+    functional.bilinear + functional.dwconv_bn on the same deferred tensor."""
+    t = act_lo.t
+    out_hw = tuple(int(v) for v in out_hw)
+    C = t.shape[-1]
+    if t.dim() != 4 or len(out_hw) != 2 or min(out_hw) < 1:
+        raise ValueError("up_dwconv_bn: a %s activation resized to %s" % (tuple(t.shape), out_hw))
+    if not (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
+            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1)
+            and conv.groups == conv.in_channels == conv.out_channels == C and conv.bias is None):
+        raise NotImplementedError(
+            "up_dwconv_bn: a bias-free depthwise 3x3 with stride 1, padding 1 and dilation 1 over "
+            "the activation's %d channels is served; got kernel_size %s stride %s padding %s "
+            "dilation %s groups %d (%d -> %d)%s"
+            % (C, tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding),
+               tuple(conv.dilation), conv.groups, conv.in_channels, conv.out_channels,
+               "" if conv.bias is None else " with a bias"))
+    if is_group_norm(bn):
+        raise NotImplementedError("up_dwconv_bn: GroupNorm is not served behind the node")
+    N = t.shape[0]
+    if not up_dw_routed(t.dtype, C, N * out_hw[0] * out_hw[1]):
+        up = bilinear(act_lo, out_hw, align_corners=align_corners)
+        return dwconv_bn(Act(up), conv, bn, out=out)
+    spec = UpDwSpec(act_lo, out_hw, align_corners, out, uses_batch_stats(bn))
+    g, b = act_lo.params
+    y = _UpDwFn.apply(t, g, b, conv.weight, spec)
+    return Act(y, finish_bn(bn, spec.partial, N * out_hw[0] * out_hw[1], y=y))

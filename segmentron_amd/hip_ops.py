@@ -2109,3 +2109,104 @@ def bilinear_pad_bwd(gy, in_hw, out_hw, place=(0, 0), align_corners=True):
              out_hw[0], out_hw[1], Hd, Wd, int(place[0]), int(place[1]), int(align_corners),
              _stream())
     return gx
+
+
+# ---- ContextNet: bilinear resize + depthwise 3x3 without the upsampled map (csrc/contextnet.hip) ----
+def up_dw_rows(dtype, N, H, W, C, kind=0):
+    """Partial rows of up_dw's statistics (kind 0) / up_dw_bwd's weight gradient (kind 1) for an
+    [N,H,W,C] output (host only)."""
+    if dtype not in _DT:
+        raise ValueError("up_dw_rows: dtype %s (float32 or bfloat16)" % (dtype,))
+    rows = LIB.query("seg_up_dw_rows", _DT[dtype], int(N), int(H), int(W), int(C), int(kind))
+    if rows < 1:
+        raise ValueError("up_dw_rows: bad shape / kind: %s %s kind %s (C a positive multiple of %d)"
+                         % (dtype, (N, H, W, C), kind, vec_of(dtype)))
+    return rows
+
+
+def _up_dw_operand(t, shape, dtype, what):
+    """-> the row pitch of an NHWC operand of up_dw / up_dw_bwd; raises instead of over-reading."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 4:
+        raise ValueError("%s: expected an NHWC 4-d tensor" % what)
+    if t.dtype not in _DT or (dtype is not None and t.dtype != dtype):
+        raise ValueError("%s: dtype %s (float32 or bfloat16, one for every operand)" % (what, t.dtype))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: expected %s, got %s" % (what, tuple(shape), tuple(t.shape)))
+    vec = vec_of(t.dtype)
+    if min(t.shape) < 1 or t.shape[-1] % vec != 0:
+        raise ValueError("%s: %s: C is a positive multiple of %d, no dimension empty"
+                         % (what, tuple(t.shape), vec))
+    if t.stride(3) != 1:
+        raise ValueError("%s: the channel dimension is not contiguous (strides %s)"
+                         % (what, t.stride()))
+    ld = nhwc(t)[4]
+    if ld % vec != 0 or t.storage_offset() % vec != 0:
+        raise ValueError("%s: row pitch %d / offset %d are no multiples of the %d-element vector"
+                         % (what, ld, t.storage_offset(), vec))
+    return ld
+
+
+def _up_dw_taps(w9c, C, like, what):
+    if not isinstance(w9c, torch.Tensor) or w9c.dtype != torch.float32 \
+            or tuple(w9c.shape) != (9, C) or not w9c.is_contiguous():
+        raise ValueError("%s: the taps are a contiguous float32 [9, %d] (tap-major)" % (what, C))
+    if w9c.device != like.device:
+        raise ValueError("%s: the taps live on %s, the activation on %s"
+                         % (what, w9c.device, like.device))
+
+
+def _up_dw_pro(pro, C, like, what):
+    mode, s, t = _pro(pro)
+    mode = int(mode)
+    if mode & PRO_AFFINE:
+        for p in (s, t):
+            if not isinstance(p, torch.Tensor) or p.dtype != torch.float32 or p.numel() != C \
+                    or not p.is_contiguous() or p.device != like.device:
+                raise ValueError("%s: the prologue's scale / shift are contiguous float32 [%d] on "
+                                 "the activation's device" % (what, C))
+    else:
+        s = t = None
+    return mode, s, t
+
+
+def up_dw(lo, out_hw, w9c, pro=None, align_corners=True, out=None, want_stats=False):
+    """y = depthwise 3x3 (zero padding 1) of bilinear(act(lo), out_hw), the upsampled map never
+    stored -> (y [N,H,W,C], partial [rows,2,C] fp32 (sum | sum of squares) or None)."""
+    N, h, w, C = lo.shape if isinstance(lo, torch.Tensor) and lo.dim() == 4 else (0, 0, 0, 0)
+    ldlo = _up_dw_operand(lo, None, None, "up_dw lo")
+    H, W = int(out_hw[0]), int(out_hw[1])
+    if H < 1 or W < 1:
+        raise ValueError("up_dw: output size %s" % ((H, W),))
+    _up_dw_taps(w9c, C, lo, "up_dw")
+    mode, s, t = _up_dw_pro(pro, C, lo, "up_dw")
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=lo.dtype, device=lo.device)
+    ldy = _up_dw_operand(out, (N, H, W, C), lo.dtype, "up_dw out")
+    rows = up_dw_rows(lo.dtype, N, H, W, C, 0)
+    partial = torch.empty((rows, 2, C), dtype=torch.float32, device=lo.device) if want_stats \
+        else None
+    LIB.call("seg_up_dw_fwd", _DT[lo.dtype], _p(lo), ldlo, N, h, w, C, mode, _p(s), _p(t),
+             _p(w9c), _p(out), ldy, H, W, int(bool(align_corners)), _p(partial), rows, _stream())
+    return out, partial
+
+
+def up_dw_bwd(dy, lo, w9c, pro=None, align_corners=True, out=None):
+    """One pass over dy [N,H,W,C] and lo -> (d_up [N,H,W,C] in the activation dtype = dy correlated
+    with the flipped taps, pw [rows,9,C] fp32 = weight-gradient rows with the upsampled map
+    recomputed from lo; dw_wgrad_finalize reduces them)."""
+    if not isinstance(dy, torch.Tensor) or dy.dim() != 4:
+        raise ValueError("up_dw_bwd dy: expected an NHWC 4-d tensor")
+    N, h, w, C = lo.shape if isinstance(lo, torch.Tensor) and lo.dim() == 4 else (0, 0, 0, 0)
+    ldlo = _up_dw_operand(lo, None, None, "up_dw_bwd lo")
+    H, W = int(dy.shape[1]), int(dy.shape[2])
+    lddy = _up_dw_operand(dy, (N, H, W, C), lo.dtype, "up_dw_bwd dy")
+    _up_dw_taps(w9c, C, lo, "up_dw_bwd")
+    mode, s, t = _up_dw_pro(pro, C, lo, "up_dw_bwd")
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=lo.dtype, device=lo.device)
+    ldd = _up_dw_operand(out, (N, H, W, C), lo.dtype, "up_dw_bwd out")
+    rows = up_dw_rows(lo.dtype, N, H, W, C, 1)
+    pw = torch.empty((rows, 9, C), dtype=torch.float32, device=lo.device)
+    LIB.call("seg_up_dw_bwd", _DT[lo.dtype], _p(dy), lddy, _p(lo), ldlo, N, h, w, C, mode, _p(s),
+             _p(t), _p(w9c), _p(out), ldd, H, W, int(bool(align_corners)), _p(pw), rows, _stream())
+    return out, pw

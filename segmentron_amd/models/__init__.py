@@ -16,3 +16,4 @@ from .espnetv2 import ESPNetV2  # noqa: F401
 from .edanet import EDANet  # noqa: F401
 from .fpenet import FPENet  # noqa: F401
 from .unet import UNet  # noqa: F401
+from .contextnet import ContextNet  # noqa: F401
